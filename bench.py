@@ -3,6 +3,7 @@
 synthetic 640x480 RGB-D, N GPUs of one node (one process per GPU, RCCL gradient all-reduce).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --steps 3 --dump-outputs DIR      # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one frame-equivalent of the reference's budget (loopy_slam_amd/workload.py):
@@ -21,6 +22,33 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_MAP_ROWS = 1 << 17         # 131 072 map rows x 67 floats = 35 MB: with the rest, the dump stays under 64 MB
+
+
+def dump_outputs(path, wl, last):
+    """--dump-outputs: what a caller of the timed path receives from its LAST timed step, one .npy per array under `path` - the
+    tracked pose and the tracking / mapping loss logs step() returns, the map it leaves (positions and both feature tables; all rows up to
+    DUMP_MAP_ROWS, beyond that a fixed seeded sample, map_rows holding their indices in float64), the decoder weight blob, and the
+    full-frame render of the last mapped frame; float32 but for map_rows.  The inputs are seeded and the mapping backward sums its gradients in a
+    fixed order, so the same arguments give the same bits in every array (tests/test_bench_cli.py) and two builds can be compared array
+    by array."""
+    import numpy as np
+    import torch
+    best, tlog, mlog = last
+    n = wl.n
+    rows = torch.arange(n) if n <= DUMP_MAP_ROWS else \
+        torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_MAP_ROWS].sort().values
+    idx = rows.to(wl.pos.device)
+    frame = wl.img_frame if wl.img_full is not None else (wl.img_state.depth, wl.img_state.var, wl.img_state.color)
+    arrays = {'pose': best, 'track_log': tlog, 'map_log': mlog,
+              'map_rows': rows.double(), 'map_pos': wl.pos[idx], 'map_geo_feats': wl.geo[idx], 'map_col_feats': wl.col[idx],
+              'decoder_blob': wl.dec.blob,
+              'render_depth': frame[0].reshape(wl.H, wl.W), 'render_var': frame[1].reshape(wl.H, wl.W), 'render_color': frame[2].reshape(wl.H, wl.W, 3)}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a if a.dtype == np.float64 else a.astype(np.float32))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -35,7 +63,11 @@ def main():
                     help='strong scaling: the per-frame ray budget is SPLIT over the ranks (R / N rays per rank and iteration) instead of '
                          'every rank bringing a full batch.  frames/s of ONE sequence is bounded by the replicated tracking and the track -> map '
                          'dependency (about 2-2.8x at 8 GPUs, DESIGN.md section 6); the 6x-at-8-GPUs target is the weak-scaling rays/s figure')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0), for comparing two builds output for output')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one process per GPU) the way the driver's torchrun line does and
@@ -126,10 +158,12 @@ def main():
     prof.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        wl.step(full=True)
+        last = wl.step(full=True)
     barrier()
     dt = time.perf_counter() - t0
     kstat = prof.stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, last)          # before the untimed steps below overwrite the map, the logs and the render
     n_mapped = (args.steps + budget.every_frame - 1) // budget.every_frame
     # the same kernel alone on the chip: one more untimed step with the library's second stream switched off
     eng.lib.check(eng.lib.dll.lk_set_serial(1), 'lk_set_serial')

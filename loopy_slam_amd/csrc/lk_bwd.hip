@@ -515,27 +515,27 @@ __global__ __launch_bounds__(256, LK_DBWD_MINB) void k_decode_bwd(LkDecodeBwdArg
     }
 }
 
-// out[j] += sum_p part[p][j].  One workgroup per (32-column group, 16 partial rows): 8 row lanes x 32 columns, two
-// rows per lane read coalesced, combined through LDS, then ONE atomic per (workgroup, column) - a few tens to a
-// hundred adds per address in total (~13 ns each when they collide), and no serial loop over the rows.
-__global__ __launch_bounds__(256) void k_reduce_partials(const float* __restrict__ part, int n_parts, int width, float* __restrict__ out) {
-    __shared__ float sh[8][32];
+// out[j] += sum_p part[p][j].  One workgroup per 32-column group walks every partial row in a fixed order (32 row lanes x 32 columns,
+// read coalesced, combined through LDS in a fixed tree) and adds ONE value per column: with several workgroups per column, the order of
+// their atomics on `out` (the rounding of the sum) changed from run to run.
+__global__ __launch_bounds__(1024) void k_reduce_partials(const float* __restrict__ part, int n_parts, int width, float* __restrict__ out) {
+    __shared__ float sh[32][33];
     const int e = (int)threadIdx.x & 31, q = (int)threadIdx.x >> 5;
     const int col = blockIdx.x * 32 + e;
-    const int p0 = blockIdx.y * 16 + q;
     float s = 0.0f;
-    if (col < width) {
-        if (p0 < n_parts) s = part[(size_t)p0 * width + col];
-        if (p0 + 8 < n_parts) s += part[(size_t)(p0 + 8) * width + col];
-    }
+    if (col < width)
+        for (int p = q; p < n_parts; p += 32) s += part[(size_t)p * width + col];
     sh[q][e] = s;
     __syncthreads();
-    if (q == 0 && col < width)
-        atomicAdd(out + col, ((sh[0][e] + sh[1][e]) + (sh[2][e] + sh[3][e])) + ((sh[4][e] + sh[5][e]) + (sh[6][e] + sh[7][e])));
+    for (int h = 16; h > 0; h >>= 1) {
+        if (q < h) sh[q][e] += sh[q + h][e];
+        __syncthreads();
+    }
+    if (q == 0 && col < width) atomicAdd(out + col, sh[0][e]);
 }
 
 int lk_launch_reduce_partials(const float* part, int n_parts, int width, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce_partials, dim3(lk_cdiv(width, 32), lk_cdiv(n_parts, 16)), dim3(256), 0, st, part, n_parts, width, out);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(lk_cdiv(width, 32)), dim3(1024), 0, st, part, n_parts, width, out);
     return LK_OK;
 }
 

@@ -139,13 +139,16 @@ __global__ __launch_bounds__(256) void k_interp_bwd_x(LkInterpBwdArgs a, Exposur
 // Now: the same sums with a fraction of the atomics.  A mapper batch touches few points many times (5 000 rays x 5 samples x 8
 // neighbours = 197 k rows on 15 k points of the benchmark frame: 12.7 rows per point), and the atomic scatter pays for every
 // row twice (two tables) at the memory-side atomic rate, with the adds of a point serialised on its line.  The rows are
-// counting-sorted by point - k_seg_count (rank of the row among the rows of its point; inside k_sample_interp when the forward
-// knows that this backward follows), an exclusive scan of the per-point counts that also clears them, k_seg_place - which only
-// needs the neighbour indices: it runs on the second stream beside the decoders.
-// k_feat_gather then gives every half-wave (32 channels) 16 consecutive rows of the sorted list: the rows of a point are
-// added in registers and flushed with ONE atomic per run (runs can continue in the next chunk) - about 27 k flushes instead
-// of 197 k, every half-wave with the same amount of work (a per-point linked list walked by its first row was slower than
-// the atomics: the longest chain sets the time).
+// counting-sorted by point - k_seg_count (counts, and an atomic rank of the row among the rows of its point; inside k_sample_interp
+// when the forward knows that this backward follows), an exclusive scan of the per-point counts that also clears them, k_seg_place,
+// then k_seg_rank_det (the rank becomes the number of the point's rows with a smaller row index) and k_seg_place again, so that the
+// list is ordered by (point, row) in every run - which only needs the neighbour indices: it runs on the second stream beside the
+// decoders.
+// k_feat_gather then gives every half-wave (32 channels) 16 consecutive rows of the sorted list; a point belongs to the half-wave
+// whose chunk holds its first row, which adds all of the point's rows in registers in list order - past its chunk's end if the run
+// goes on - and flushes them with ONE atomic per point, so the sums repeat bit for bit (about 27 k flushes instead of 197 k).  A
+// half-wave's work is its chunk plus the tail of its last point's run: a per-point linked list walked by its first row, with every
+// point's whole chain on one half-wave, was slower than the atomics (the longest chain sets the time).
 __global__ __launch_bounds__(256) void k_seg_count(LkFeatScatterArgs a) {
     const long long row = (long long)blockIdx.x * 256 + (int)threadIdx.x;
     if (row >= (long long)a.P * LK_K) return;
@@ -173,6 +176,23 @@ __global__ __launch_bounds__(256) void k_seg_place(LkFeatScatterArgs a) {
         a.seg_list[base + off[a.key_of ? a.key_of[idx] : idx] + rk] = (int)row;
     }
     if (row == 0 && a.seg_total) a.seg_total[y] = off[a.N];
+}
+
+// The count pass hands out ranks with an atomic, so the order of a point's rows in the list changed from run to run, and with it the order
+// in which k_feat_gather adds them.  This pass replaces the rank by the number of rows of the same point with a smaller row index, and
+// k_seg_place runs again: the list is sorted by (point, row) every run.
+__global__ __launch_bounds__(256) void k_seg_rank_det(LkFeatScatterArgs a) {
+    const long long row = (long long)blockIdx.x * 256 + (int)threadIdx.x;
+    if (row >= (long long)a.P * LK_K) return;
+    const int y = (int)blockIdx.y;
+    const long long base = (long long)y * a.P * LK_K;
+    if (a.seg_rank[base + row] < 0) return;
+    const int32_t* __restrict__ off = a.seg_off + (size_t)y * a.cnt_stride;
+    const int idx = a.nbr_idx[base + row];
+    const int key = a.key_of ? a.key_of[idx] : idx;
+    int rk = 0;
+    for (int i = off[key], e = off[key + 1]; i < e; ++i) rk += a.seg_list[base + i] < (int)row;
+    a.seg_rank[base + row] = rk;
 }
 
 // linear2 of the rel-pos MLP (see k_dw2_hbar below) as a body: block bx of nb.  LDS for 32 samples at a time (20 KB: as a rider of k_feat_gather
@@ -245,18 +265,26 @@ __global__ __launch_bounds__(256) void k_feat_gather(LkFeatScatterArgs a) {
         return;
     }
     const int c = (int)threadIdx.x & 31;
-    const long long i0 = ((long long)bx * 8 + ((int)threadIdx.x >> 5)) * LK_GATHER_CHUNK;
+    long long i0 = ((long long)bx * 8 + ((int)threadIdx.x >> 5)) * LK_GATHER_CHUNK;
     const int total = a.seg_total ? *a.seg_total : a.seg_off[a.N];
     if (i0 >= total) return;
-    const int n = min(LK_GATHER_CHUNK, (int)(total - i0));
+    // every point is summed by the half-wave whose chunk holds its first row, in list order, and flushed with ONE atomic: a point whose
+    // rows ran over chunk boundaries took three or more atomics, and their order (the sum's rounding) changed from run to run
+    const long long e = min(i0 + LK_GATHER_CHUNK, (long long)total);
+    if (i0 > 0) {
+        const int prev = a.nbr_idx[a.seg_list[i0 - 1]];
+        while (i0 < e && a.nbr_idx[a.seg_list[i0]] == prev) ++i0;
+        if (i0 == e) return;
+    }
+    // the chunk's rows, then - four at a time, no separate scan for the run's end - the rest of the run of the chunk's last point
     const bool col = a.dfeat != nullptr || a.dc_col != nullptr;
     int cur = -1;
     float sg = 0.0f, sc = 0.0f;
-    for (int b = 0; b < n; b += 4) {                       // four rows per step: their loads are independent
+    for (long long b = i0; b < total; b += 4) {               // four rows per step: their loads are independent
         int row[4], idx[4];
         float vg[4], vc[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) row[u] = a.seg_list[i0 + min(b + u, n - 1)];
+        for (int u = 0; u < 4; ++u) row[u] = a.seg_list[min(b + u, (long long)total - 1)];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             idx[u] = a.nbr_idx[row[u]];
@@ -265,10 +293,12 @@ __global__ __launch_bounds__(256) void k_feat_gather(LkFeatScatterArgs a) {
             vg[u] = w * a.dc_geo[(size_t)s * LK_C + c];
             vc[u] = a.dfeat ? a.dfeat[(size_t)row[u] * LK_C + c] : (a.dc_col ? w * a.dc_col[(size_t)s * LK_C + c] : 0.0f);
         }
+        bool done = false;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            if (b + u >= n) break;
+            if (done || b + u >= total) { done = true; continue; }
             if (idx[u] != cur) {
+                if (b + u >= e) { done = true; continue; }     // past the chunk: only the run of its last point goes on
                 if (cur >= 0) {
                     atomicAdd(a.g_geo_feats + (size_t)cur * LK_C + c, sg);
                     if (col) atomicAdd(a.g_col_feats + (size_t)cur * LK_C + c, sc);
@@ -278,6 +308,7 @@ __global__ __launch_bounds__(256) void k_feat_gather(LkFeatScatterArgs a) {
             }
             sg += vg[u]; sc += vc[u];
         }
+        if (done) break;
     }
     atomicAdd(a.g_geo_feats + (size_t)cur * LK_C + c, sg);
     if (col) atomicAdd(a.g_col_feats + (size_t)cur * LK_C + c, sc);
@@ -1430,6 +1461,8 @@ int lk_launch_seg_sort(const LkFeatScatterArgs& a, bool counted, hipStream_t st,
     // seg_cnt is zero on entry: the scan of the previous sort cleared what that sort had counted
     if (!counted) hipLaunchKernelGGL(k_seg_count, dim3(nb, batch), dim3(256), 0, st, a);
     lk_launch_scan_i32(a.seg_cnt, a.seg_off, a.seg_sums, a.N + 1, st, batch, a.cnt_stride, a.sums_stride);
+    hipLaunchKernelGGL(k_seg_place, dim3(nb, batch), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_seg_rank_det, dim3(nb, batch), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_seg_place, dim3(nb, batch), dim3(256), 0, st, a);
     return LK_OK;
 }

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,8 +27,13 @@ def _bench(args, env=None, timeout=900):
 
 
 @pytest.fixture(scope='module')
-def plain():
-    return _bench(['--steps', '5', '--warmup', '1', '--no-cpu-baseline'])
+def dump_dir(tmp_path_factory):
+    return tmp_path_factory.mktemp('bench_outputs')
+
+
+@pytest.fixture(scope='module')
+def plain(dump_dir):
+    return _bench(['--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--dump-outputs', str(dump_dir)])
 
 
 def test_default_line_carries_the_three_budgets(plain):
@@ -51,6 +57,31 @@ def test_default_line_carries_the_three_budgets(plain):
     assert 0.85 < big['ms_per_step'] / d['ms_per_step'] < 1.25
     assert 4_990_000 < ref['n_points'] < 5_010_000 and ref['iterations'] == 300 and 'float16' in ref['feature_tables']
     assert 0.05 < ref['ms_per_iteration'] < 1.0          # (dense Adam over 5 M rows was 1.0 / 2.0 ms per geometry / colour iteration, profiles/r3_refine.md)
+
+
+def test_dump_outputs_of_the_last_timed_step(plain, dump_dir):
+    """--dump-outputs: the arrays the last timed step handed back - pose, loss logs, the map (every row while it fits), decoder blob, the
+    mapped frame's full render - as float32 / float64 .npy, finite, 64 MB at most; --steps is the number of timed steps."""
+    a = {p.stem: np.load(p) for p in dump_dir.glob('*.npy')}
+    assert set(a) == {'pose', 'track_log', 'map_log', 'map_rows', 'map_pos', 'map_geo_feats', 'map_col_feats', 'decoder_blob',
+                      'render_depth', 'render_var', 'render_color'}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a['pose'].shape == (7,) and a['track_log'].shape == (40, 4) and a['map_log'].shape == (60, 4)
+    assert a['render_depth'].shape == (480, 640) and a['render_color'].shape == (480, 640, 3)
+    n = a['map_rows'].shape[0]
+    assert np.array_equal(a['map_rows'], np.arange(n)) and a['map_pos'].shape == (n, 3) and a['map_geo_feats'].shape == (n, 32)
+    assert plain['steps'] == 5 and plain['ms_per_step'] > 0
+
+
+def test_dump_outputs_repeat_bit_for_bit(plain, dump_dir, tmp_path):
+    """The same command again: seeded inputs and fixed-order reductions give the same bits in every dumped array (the pose, both loss
+    logs, the map, the decoder blob and the full-frame render after 5 timed steps of 100 tracking and mapping iterations each)."""
+    _bench(['--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--dump-outputs', str(tmp_path)])
+    a = {p.stem: np.load(p) for p in dump_dir.glob('*.npy')}
+    b = {p.stem: np.load(p) for p in tmp_path.glob('*.npy')}
+    assert set(a) == set(b) and len(a) == 11
+    assert not [k for k in a if not np.array_equal(a[k], b[k])]
 
 
 def test_two_ranks_on_one_device_command_line():

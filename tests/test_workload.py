@@ -59,3 +59,39 @@ def test_frame_workload_steps(backend, name):
         assert float((wl.exposure_feats[-1].detach() - xf0[-1]).abs().max()) > 1e-4
         assert all(torch.equal(f.detach(), f0) for f, f0 in zip(wl.exposure_feats[:-1], xf0[:-1]))
         assert all(float((p.detach() - p0).abs().max()) > 1e-5 for p, p0 in zip(wl.mlp_exposure.parameters(), xw0))
+
+
+def test_bench_dump_is_the_last_step(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.dump_outputs) writes what the last step returned and left behind: pose and loss logs as step()
+    returned them, the map's rows, the decoder blob and the last mapped frame's render - every map row while they fit, above
+    DUMP_MAP_ROWS a sorted sample drawn from a fixed seed (the same rows in every run)."""
+    import bench
+    eng = make_engine('emu')
+    b = _budget('replica', 'emu')
+    cam = dict(H=48, W=64, fx=51.7, fy=51.6, cx=31.9, cy=25.5)
+    pos, geo, col = (t.to(eng.device) for t in syn.build_cloud(b.n_points, device='cpu', seed=3, intr=cam))
+    b.ignore_edge = 4
+    wl = workload.FrameWorkload(eng, b, cloud=(pos, geo, col, 1), intr=cam)
+    for _ in range(2):
+        last = wl.step(full=True)
+
+    def dump(name):
+        bench.dump_outputs(str(tmp_path / name), wl, last)
+        return {p.stem: np.load(p) for p in (tmp_path / name).glob('*.npy')}
+
+    full = dump('full')
+    monkeypatch.setattr(bench, 'DUMP_MAP_ROWS', 1000)
+    s1, s2 = dump('s1'), dump('s2')
+    for a in (full, s1):
+        assert all(v.dtype == (np.float64 if k == 'map_rows' else np.float32) for k, v in a.items())
+        for k, t in (('pose', last[0]), ('track_log', last[1]), ('map_log', last[2]), ('decoder_blob', wl.dec.blob)):
+            assert np.array_equal(a[k], t.cpu().numpy()), k
+        assert np.array_equal(a['render_depth'].reshape(-1), wl.img_state.depth.cpu().numpy())
+        assert np.array_equal(a['render_color'].reshape(-1, 3), wl.img_state.color.cpu().numpy())
+        rows = a['map_rows'].astype(np.int64)
+        for k, t in (('map_pos', wl.pos), ('map_geo_feats', wl.geo), ('map_col_feats', wl.col)):
+            assert np.array_equal(a[k], t[:wl.n].cpu().numpy()[rows]), k
+    assert np.array_equal(full['map_rows'], np.arange(wl.n))
+    r = s1['map_rows']
+    assert r.shape == (1000,) and (np.diff(r) > 0).all() and r[0] >= 0 and r[-1] < wl.n
+    assert set(s1) == set(s2) and all(np.array_equal(s1[k], s2[k]) for k in s1)
