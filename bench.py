@@ -4,14 +4,19 @@ synthetic 640x480 RGB-D, N GPUs of one node (one process per GPU, RCCL gradient 
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     python bench.py --steps 3 --dump-outputs DIR      # + what the last timed step computed, as DIR/<name>.npy
+    python bench.py --steps 3 --full                  # + everything else the benchmark measures (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one frame-equivalent of the reference's budget (loopy_slam_amd/workload.py):
 40 tracking iterations x 1500 rays + 60 mapping iterations x 5000 rays (24 geometry + 36 colour),
 each iteration = ray gather, inside-mask, render forward, loss, render backward, Adam - and on every 5th step (a mapped
-frame) the frame's point insertion + index rebuild + full-frame render (the headline since round 4; the iterations alone
-are reported beside it as ms_per_step_iterations).
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for how roofline / cpu_baseline are obtained.
+frame) the frame's point insertion + index rebuild + full-frame render (the headline since round 4).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline.  --full also measures what takes
+steps or runs of its own: per-kernel timing and the roofline of the dominant kernel (HIP events in an extra step and around that
+kernel in the timed steps), the same kernel with one stream, the iterations alone (ms_per_step_iterations), the steps with frames
+uploaded from host memory, the TUM / ScanNet budgets and the 2 M / 5 M-point maps (`workloads`, one rank) and the CPU baseline.
+Both print ONE JSON line (rank 0) and time the same steps from the same state, so they dump the same outputs.
+See DESIGN.md §Measurement for how roofline / cpu_baseline are obtained.
 """
 import argparse
 import json
@@ -55,10 +60,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes steps or runs of its own: per-kernel timing and rooflines, the dominant kernel with one stream, '
+                         'the iterations alone, frames from host memory, the other budgets and map sizes (`workloads`) and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--points', type=int, default=100_000)
     ap.add_argument('--headline-only', action='store_true',
-                    help='skip the TUM / ScanNet budgets (`workloads`): profiling passes, whose per-kernel averages must be those of the headline workload')
+                    help='with --full: skip the TUM / ScanNet budgets (`workloads`): profiling passes, whose per-kernel averages must be those of the headline workload')
     ap.add_argument('--strong', action='store_true',
                     help='strong scaling: the per-frame ray budget is SPLIT over the ranks (R / N rays per rank and iteration) instead of '
                          'every rank bringing a full batch.  frames/s of ONE sequence is bounded by the replicated tracking and the track -> map '
@@ -127,8 +135,9 @@ def main():
     if args.strong and world > 1:
         budget.map_rays = max(32, budget.map_rays // world)          # tracking is replicated (not sharded) in either mode
     wl = workload.FrameWorkload(eng, budget, dist=dctx)
-    cloud_dev = tuple(t[:wl.n].clone() for t in (wl.pos, wl.geo, wl.col)) + (wl.n_rooms,) if (world == 1 and not force_dist) else None
-    cloud0 = tuple(t[:wl.n].cpu() for t in (wl.pos, wl.geo, wl.col)) if (rank == 0 and not args.no_cpu_baseline) else None
+    # --full: the map as built, for the other budgets (one rank) and the CPU baseline - the steps below change it
+    cloud_dev = tuple(t[:wl.n].clone() for t in (wl.pos, wl.geo, wl.col)) + (wl.n_rooms,) if (args.full and world == 1 and not force_dist) else None
+    cloud0 = tuple(t[:wl.n].cpu() for t in (wl.pos, wl.geo, wl.col)) if (args.full and rank == 0 and not args.no_cpu_baseline) else None
 
     def barrier():
         if world > 1:
@@ -137,15 +146,18 @@ def main():
 
     for _ in range(args.warmup):
         wl.step()
-    # one extra untimed step with HIP events around EVERY kernel picks the dominant kernel of this workload ...
+    # one extra untimed step; with --full, HIP events around EVERY kernel of it pick the dominant kernel of this workload ...
+    # (a plain run takes the same step without them: the timed steps start from the same state either way)
     barrier()
-    prof_all = profile.KernelTimer(eng, '*')
-    prof_all.start()
+    if args.full:
+        prof_all = profile.KernelTimer(eng, '*')
+        prof_all.start()
     wl.step()
     barrier()
-    kall = prof_all.stop()
-    dominant = os.environ.get('BENCH_ROOFLINE_KERNEL') or profile.dominant_kernel(
-        {k: v for k, v in kall.items() if k in profile.work_per_step(budget)})
+    if args.full:
+        kall = prof_all.stop()
+        dominant = os.environ.get('BENCH_ROOFLINE_KERNEL') or profile.dominant_kernel(
+            {k: v for k, v in kall.items() if k in profile.work_per_step(budget)})
     # ... and the timed region records events on the launch stream around that kernel only.
     # THE TIMED STEP IS THE FULL STEP: 40 tracking + 60 mapping iterations per frame and, on every 5th step (a MAPPED frame of the
     # reference's schedule, mapping.every_frame), what that frame does around its iterations - insertion of 6 000 pixels through the
@@ -153,52 +165,56 @@ def main():
     wl.frame_no = 0
     wl.step(full=True)                  # untimed: first-use allocations of the full-frame render state
     wl.frame_no = 0
-    prof = profile.KernelTimer(eng, dominant)
     barrier()
-    prof.start()
+    if args.full:
+        prof = profile.KernelTimer(eng, dominant)
+        prof.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         last = wl.step(full=True)
     barrier()
     dt = time.perf_counter() - t0
-    kstat = prof.stop()
+    if args.full:
+        kstat = prof.stop()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, wl, last)          # before the untimed steps below overwrite the map, the logs and the render
     n_mapped = (args.steps + budget.every_frame - 1) // budget.every_frame
-    # the same kernel alone on the chip: one more untimed step with the library's second stream switched off
-    eng.lib.check(eng.lib.dll.lk_set_serial(1), 'lk_set_serial')
-    barrier()
-    prof_s = profile.KernelTimer(eng, dominant)
-    prof_s.start()
-    wl.step()
-    barrier()
-    kstat_serial = prof_s.stop()
-    eng.lib.check(eng.lib.dll.lk_set_serial(0), 'lk_set_serial')
-    # beside it: the iterations alone (no mapped-frame extras) - the figure rounds 1-3 reported as `value`
-    barrier()
-    t0i = time.perf_counter()
-    for _ in range(args.steps):
+    others = {}
+    if args.full:
+        # the same kernel alone on the chip: one more untimed step with the library's second stream switched off
+        eng.lib.check(eng.lib.dll.lk_set_serial(1), 'lk_set_serial')
+        barrier()
+        prof_s = profile.KernelTimer(eng, dominant)
+        prof_s.start()
         wl.step()
-    barrier()
-    dt_iter = time.perf_counter() - t0i
-    # PCIe-inclusive: the C ABI takes DEVICE pointers, so a caller that receives its RGB-D frames in host memory uploads one frame
-    # (640 x 480 fp32 depth + RGB = 4.9 MB) per step; the same timed steps with that upload from pinned memory in front of each
-    # (reported beside `value`, never as `value`)
-    host_d, host_c = wl.depth_stack.cpu().pin_memory(), wl.color_stack.cpu().pin_memory()      # every frame of the window: contents unchanged
-    wl.frame_no = 0
-    barrier()
-    t0h = time.perf_counter()
-    for _ in range(args.steps):
-        k = wl.frame_no % budget.window
-        wl.depth_stack[k].copy_(host_d[k], non_blocking=True)
-        wl.color_stack[k].copy_(host_c[k], non_blocking=True)
-        wl.step(full=True)
-    barrier()
-    dt_host = time.perf_counter() - t0h
+        barrier()
+        kstat_serial = prof_s.stop()
+        eng.lib.check(eng.lib.dll.lk_set_serial(0), 'lk_set_serial')
+        # beside it: the iterations alone (no mapped-frame extras) - the figure rounds 1-3 reported as `value`
+        barrier()
+        t0i = time.perf_counter()
+        for _ in range(args.steps):
+            wl.step()
+        barrier()
+        dt_iter = time.perf_counter() - t0i
+        # PCIe-inclusive: the C ABI takes DEVICE pointers, so a caller that receives its RGB-D frames in host memory uploads one frame
+        # (640 x 480 fp32 depth + RGB = 4.9 MB) per step; the same timed steps with that upload from pinned memory in front of each
+        # (reported beside `value`, never as `value`)
+        host_d, host_c = wl.depth_stack.cpu().pin_memory(), wl.color_stack.cpu().pin_memory()      # every frame of the window: contents unchanged
+        wl.frame_no = 0
+        barrier()
+        t0h = time.perf_counter()
+        for _ in range(args.steps):
+            k = wl.frame_no % budget.window
+            wl.depth_stack[k].copy_(host_d[k], non_blocking=True)
+            wl.color_stack[k].copy_(host_c[k], non_blocking=True)
+            wl.step(full=True)
+        barrier()
+        dt_host = time.perf_counter() - t0h
     # The other two single-GPU budgets of BASELINE.json (configs 3-5's 1-GPU content) on the same map: TUM (200 x 5 000 tracking from the
     # gradient-pixel pool + 150 x 10 000 mapping per frame, dynamic radii) and ScanNet (100 x 5 000 + 60 x 10 000, exposure encoding) -
     # 3 timed FULL steps each (their mapped-frame extras included on the budget's own every_frame schedule), reported under `workloads`
-    others = {}
+    # (--full: cloud_dev is None in a plain run)
     if cloud_dev is not None and not args.headline_only:
         del wl.mapper, wl.tracker
         for name, mk in (('tum', workload.Budget.tum), ('scannet', workload.Budget.scannet)):
@@ -268,9 +284,11 @@ def main():
                                                f'{ref.n}-point map trainable (rows = NULL: only rows that received a gradient are stepped), colour decoder frozen'}
         del mo, ref, geo16, col16
     if world > 1:
-        t = torch.tensor([dt, dt_iter, dt_host], device='cuda')
+        t = torch.tensor([dt, dt_iter, dt_host] if args.full else [dt], device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_iter, dt_host = float(t[0].item()), float(t[1].item()), float(t[2].item())
+        dt = float(t[0].item())
+        if args.full:
+            dt_iter, dt_host = float(t[1].item()), float(t[2].item())
     rays_per_step = budget.rays_per_frame
     # whole-job rays of a step: every rank brings its own mapping rays; the tracking iterations are REPLICATED on the ranks (the same
     # rays everywhere, no exchange - steps.TrackOptimizer), so they count once however many ranks repeat them
@@ -287,10 +305,11 @@ def main():
         'step': f'the FULL step: every {budget.every_frame}th of the {args.steps} timed steps ({n_mapped} of them) is a mapped frame that also inserts '
                 f'{budget.pixels_adding} pixels (lk_add_points + feature rows + lk_knn_build, Mapper.py:421-482) and renders the 640x480 frame '
                 f'(307 200 rays, Mapper.py:966-969; these rays are NOT counted in `value`' + (', on a stream of its own beside the next frames\' tracking' if wl.render_stream is not None else '') + f'); {wl.n_added} points added over the run, map {wl.n} points',
-        # the iterations alone (what rounds 1-3 reported as the headline)
-        'ms_per_step_iterations': 1e3 * dt_iter / args.steps, 'frames_per_s_iterations': args.steps / dt_iter,
-        'ms_per_step_host_frames': 1e3 * dt_host / args.steps,
-        'host_frames': 'the same steps with one RGB-D frame (4.9 MB, pinned host memory) uploaded over PCIe in front of each - the boundary takes device pointers',
+        # --full: the iterations alone (what rounds 1-3 reported as the headline) and the steps with frames from host memory
+        **({'ms_per_step_iterations': 1e3 * dt_iter / args.steps, 'frames_per_s_iterations': args.steps / dt_iter,
+            'ms_per_step_host_frames': 1e3 * dt_host / args.steps,
+            'host_frames': 'the same steps with one RGB-D frame (4.9 MB, pinned host memory) uploaded over PCIe in front of each - the boundary takes device pointers'}
+           if args.full else {}),
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': 1e3 * dt / args.steps, 'higher_is_better': True, 'scaling': 'strong' if (args.strong and world > 1) else 'weak',
         'vs_baseline': None,
@@ -304,18 +323,20 @@ def main():
                    'parallelism': f'dp{world} (mapping ray-sharded with one gradient all-reduce per iteration; tracking replicated)'},
     }
     if rank == 0:
-        out['roofline'] = profile.roofline(kstat, budget, dominant)
-        ser = profile.roofline(kstat_serial, budget, dominant)
-        if out['roofline'] is not None and ser is not None:
-            out['roofline']['serial'] = {k: ser[k] for k in ('avg_launch_us', 'achieved', 'frac') if k in ser}
-            out['roofline']['serial']['note'] = 'same kernel with the side stream off (lk_set_serial): nothing else shares the chip'
-        if out['roofline'] is not None:
-            out['roofline']['chosen_by'] = ('largest summed duration in the profiled step (kernels within 3 % of it are level and the longer average launch decides); '
-                                            'every kernel is in roofline_all_kernels')
+        if args.full:
+            out['roofline'] = profile.roofline(kstat, budget, dominant)
+            ser = profile.roofline(kstat_serial, budget, dominant)
+            if out['roofline'] is not None and ser is not None:
+                out['roofline']['serial'] = {k: ser[k] for k in ('avg_launch_us', 'achieved', 'frac') if k in ser}
+                out['roofline']['serial']['note'] = 'same kernel with the side stream off (lk_set_serial): nothing else shares the chip'
+            if out['roofline'] is not None:
+                out['roofline']['chosen_by'] = ('largest summed duration in the profiled step (kernels within 3 % of it are level and the longer average launch decides); '
+                                                'every kernel is in roofline_all_kernels')
         # north_star: fraction of the HBM roofline of the whole step (11.1 KB/ray forward, +20.5 KB/ray backward with the
         # feature-gradient scatter; tracking iterations have no scatter: 2 x 11.1 KB/ray)
         step_bytes = world * (budget.map_iters * budget.map_rays * 31.6e3 + budget.track_iters * budget.track_rays * 22.2e3)
         out['hbm_frac_whole_step'] = step_bytes * args.steps / dt / (world * profile.PEAK_HBM_GBS * 1e9)
+    if rank == 0 and args.full:
         # the same step against the fp32 matrix roof SURVEY 8d names: algorithmic MLP FLOPs (forward + backward-data + weight gradients of
         # every iteration, profile.step_flops) / time / 157.3 TFLOP/s
         if out['roofline'] is not None:
