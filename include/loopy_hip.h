@@ -528,6 +528,43 @@ int lk_wgrad_single(const float* A, int32_t lda, int32_t a_mode, const float* A2
                     const float* B, int32_t ldb, int32_t N, int32_t K, int64_t rows,
                     float* dW, int32_t ldw, float* db, int32_t chunk, void* stream);
 
+/* ---------------------------------------------------------------- loop closure: segment registration and map correction
+ * The per-point work of the reference's loop closure (src/common.py: estimate_normals / pairwise_registration /
+ * register_point_cloud_pair around Open3D; src/neural_point.py: apply_transformation).  Place recognition and the pose graph
+ * are the caller's (loopy_slam_amd/loop_closure.py); these three calls are what touches every point.
+ *
+ * lk_normals: for every point i of the cloud pos[N,3] that `knn` was built over, the covariance of ALL indexed points with
+ * d2 <= radius^2 (contract distance, the point itself included; Open3D's hybrid search would stop at the 50 nearest), and the unit
+ * eigenvector of its smallest eigenvalue (fp32 Jacobi), flipped to face host_camera3 (HOST pointer, 3 floats).  Fewer than 3
+ * neighbours: out_valid[i] = 0 and a zero normal.  The sums follow the grid's cell order, which one build fixes: repeated calls on one
+ * build are bit-identical, a rebuilt index may differ in the last bits. */
+int lk_normals(lk_knn_t knn, const float* pos, int64_t N, float radius, const float* host_camera3,
+               float* out_normals /*[N,3]*/, uint8_t* out_valid /*[N]*/, void* stream);
+/* One Gauss-Newton step's sums of point-to-plane ICP, or the sums of the correspondence information matrix.
+ * Every source point p of src[P,3] is moved by the row-major 3 x 4 transform host_T12 (HOST pointer; three fused multiply-adds per
+ * coordinate, s_x = fma(T00, p_x, fma(T01, p_y, fma(T02, p_z, T03))), so the identity reproduces p exactly); its correspondence is the
+ * nearest point q of the index under the contract above with d2 <= fl(max_dist * max_dist), order (d2, index); out_corr[P] (or NULL)
+ * receives its index, -1 if there is none.  tgt_pos[N,3] is the array the index was built over.
+ *   LK_ICP_POINT_TO_PLANE: correspondences whose target normal is valid contribute r = n.(s - q), J = [s x n | n],
+ *     w = (1 - (r/k)^2)^2 for |r| <= k else 0 (tukey_k <= 0: w = 1):
+ *     out_sums[0..20] = upper triangle of sum w J^T J row by row, [21..26] = sum w J^T r, [27] = their count, [28] = sum d2,
+ *     [29] = sum w r^2, [30..31] = 0.
+ *   LK_ICP_INFORMATION: every correspondence contributes G = [-[q]x | I] (normals may be NULL):
+ *     out_sums[0..20] = upper triangle of sum G^T G, [27] = count, [28] = sum d2, the rest 0.
+ * out_sums: LK_ICP_SUMS doubles in DEVICE memory.  scratch: lk_icp_scratch_floats(P) floats (one row of fp32 partials per workgroup).
+ * The reduction has a fixed order (lane -> wave -> workgroup row -> rows ascending in fp64, no atomics): equal inputs give equal bits. */
+#define LK_ICP_POINT_TO_PLANE 0
+#define LK_ICP_INFORMATION 1
+#define LK_ICP_SUMS 32
+int64_t lk_icp_scratch_floats(int64_t P);
+int lk_icp_accumulate(lk_knn_t tgt, const float* tgt_pos, const float* tgt_normals, const uint8_t* tgt_valid, const float* src,
+                      int64_t P, const float* host_T12, float max_dist, float tukey_k, int32_t mode, int32_t* out_corr,
+                      float* scratch, int64_t scratch_floats, double* out_sums, void* stream);
+/* In place on pos[N,3]: p <- R[s] p + t[s], s = seg_id[i], mats[n_seg][12] row-major 3 x 4 in device memory (three fused
+ * multiply-adds per coordinate).  Rows whose matrix is exactly the identity, and rows with s outside [0, n_seg), keep their bits.
+ * The neighbour index is stale afterwards: lk_knn_build. */
+int lk_apply_correction(float* pos, int64_t N, const int32_t* seg_id, const float* mats, int32_t n_seg, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -36,6 +36,7 @@ STATUS_WEIGHT_RANGE, STATUS_ACT_RANGE = 1, 2
 ERR_RANGE = -4
 
 EXPOSURE_MAX_F = 32
+ICP_POINT_TO_PLANE, ICP_INFORMATION, ICP_SUMS = 0, 1, 32
 ADAM_MAX_SEG = 16
 
 _fp = C.c_void_p     # every device pointer crosses the ABI as an integer address
@@ -208,6 +209,11 @@ class LoopyLib:
             ('lk_knn_flag_rows', [C.c_void_p, _fp, C.c_int64, C.c_void_p], C.c_int),
             ('lk_map_wait_lists', [C.POINTER(MapDesc), C.c_int32, C.c_void_p], C.c_int),
             ('lk_map_wait_rows', [C.POINTER(MapDesc), C.c_void_p], C.c_int),
+            ('lk_normals', [C.c_void_p, _fp, C.c_int64, C.c_float, C.POINTER(C.c_float), _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_icp_scratch_floats', [C.c_int64], C.c_int64),
+            ('lk_icp_accumulate', [C.c_void_p, _fp, _fp, _fp, _fp, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, _fp,
+                                   _fp, C.c_int64, _fp, C.c_void_p], C.c_int),
+            ('lk_apply_correction', [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

@@ -437,3 +437,6 @@ int lk_occupancy_relpos_fwd();
 int lk_occupancy_decode_bwd();
 int lk_occupancy_relpos_bwd_fused();
 int lk_occupancy_wgrad();
+
+// loop-closure sums (lk_reg.hip): floats per workgroup row of partials = doubles of lk_icp_accumulate's result (loopy_hip.h lists the slots)
+#define LK_REG_OUT LK_ICP_SUMS

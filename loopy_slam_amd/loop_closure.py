@@ -1,0 +1,494 @@
+"""Loop closure, geometric back end: register map segments, optimise the segment pose graph, move the map.
+
+Reference                                                  here
+  src/common.py  pairwise_registration (Open3D ICP)        register_pair -> icp -> lk_icp_accumulate (device sums, 6 x 6 solve on the host)
+  src/common.py  estimate_normals / orient_normals         estimate_normals -> lk_normals
+  get_information_matrix_from_point_clouds                 information_matrix -> lk_icp_accumulate (LK_ICP_INFORMATION)
+  src/common.py  register_point_cloud_pair                 register_pair's success rule
+  o3d global_optimization (Levenberg-Marquardt)            optimize_pose_graph (host, fp64)
+  src/neural_point.py  apply_correction / apply_transformation   LoopCloser.apply -> lk_apply_correction + lk_knn_build
+
+Out of scope: place recognition (ORB + DBoW) and the FPFH + RANSAC global alignment - every registration starts from the tracked
+poses (the identity between two segments of one world frame: the reference's method == "icp" branch, plus the Tukey fine stage of
+its "robust_icp" branch); which pairs are registered is `loop_closure.candidates` ('pose' or a callable).  TSDF fusion and the error
+plots are out as well.  What is registered are the segments' NEURAL points (on the device, thinned by the insertion radius), not
+the raw back-projected sensor points the reference keeps per fragment.  Of the reference's edge filters only the
+`old_trans_mag_filter` branch (its default) is built.  Feature rows are not touched (rotation-agnostic in the reference too).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _ffi, core
+from ._ffi import ptr
+
+COARSE_DIST, FINE_DIST, TUKEY_K, NORMAL_RADIUS = 0.3, 0.03, 0.01, 0.1      # src/common.py:594-595, 607, 647
+METHODS = ('identity', 'icp', 'robust_icp')
+
+
+# ------------------------------------------------------------------------------------------------ SE(3), fp64, vectors (omega, v)
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def se3_exp(x):
+    x = np.asarray(x, dtype=np.float64)
+    w, v = x[:3], x[3:]
+    th = float(np.linalg.norm(w))
+    K = _hat(w)
+    if th < 1e-6:
+        a, b, c = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0, 1.0 / 6.0 - th * th / 120.0
+    else:
+        a, b, c = np.sin(th) / th, (1.0 - np.cos(th)) / th ** 2, (th - np.sin(th)) / th ** 3
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + a * K + b * K @ K
+    T[:3, 3] = (np.eye(3) + b * K + c * K @ K) @ v
+    return T
+
+
+def se3_log(T):
+    T = np.asarray(T, dtype=np.float64)
+    R, t = T[:3, :3], T[:3, 3]
+    a = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])       # sin(th) * axis
+    s, c = float(np.linalg.norm(a)), 0.5 * (np.trace(R) - 1.0)
+    th = float(np.arctan2(s, c))
+    w = a * (th / s) if s > 1e-9 else a
+    K = _hat(w)
+    if th < 1e-6:
+        k = 1.0 / 12.0
+    else:
+        k = (1.0 - th * np.sin(th) / (2.0 * (1.0 - np.cos(th)))) / th ** 2
+    v = (np.eye(3) - 0.5 * K + k * K @ K) @ t
+    return np.concatenate([w, v])
+
+
+def _adjoint(T):
+    R, t = T[:3, :3], T[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = R
+    A[3:, 3:] = R
+    A[3:, :3] = _hat(t) @ R
+    return A
+
+
+def _inv(T):
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ device layer
+class SegmentCloud:
+    """The points of one segment on the device with what a registration needs of them: one grid index and the normals.
+
+    One index with NORMAL_RADIUS cells serves all three searches: the normals' radius equals the cell edge (3 x 3 rows of cells), the
+    0.3-m coarse search is the index's two-phase search (the box of one cell edge first, the full box only for a point with no
+    neighbour that near), the 0.03-m fine search touches at most 2 x 2 rows."""
+
+    def __init__(self, eng, pos, camera, cell=NORMAL_RADIUS):
+        self.eng = eng
+        self.pos = pos.detach().to(eng.device, torch.float32).contiguous()
+        self.camera = np.asarray(torch.as_tensor(camera).detach().cpu().numpy(), dtype=np.float64).reshape(-1)[:3]
+        self.cell = float(cell)
+        self._knn = self._normals = None
+
+    def __len__(self):
+        return int(self.pos.shape[0])
+
+    @property
+    def knn(self):
+        if self._knn is None:
+            self._knn = core.KnnIndex(self.eng, capacity=max(len(self), 1), cell_size=self.cell)
+            self._knn.build(self.pos)
+        return self._knn
+
+    @property
+    def normals(self):
+        if self._normals is None:
+            self._normals = estimate_normals(self.eng, self.pos, NORMAL_RADIUS, self.camera, knn=self.knn)
+        return self._normals
+
+    def close(self):
+        if self._knn is not None:
+            self._knn.close()
+            self._knn = None
+
+
+def estimate_normals(eng, pos, radius=NORMAL_RADIUS, camera=(0.0, 0.0, 0.0), knn=None):
+    """(normals [N,3] f32, valid [N] uint8) of the cloud pos (lk_normals); knn: an index already built over pos."""
+    pos = pos.contiguous()
+    N = int(pos.shape[0])
+    own = knn is None
+    if own:
+        knn = core.KnnIndex(eng, capacity=max(N, 1), cell_size=radius)
+        knn.build(pos)
+    normals, valid = eng.zeros(N, 3), eng.zeros(N, dtype=torch.uint8)
+    cam = (C.c_float * 3)(*[float(c) for c in np.asarray(camera, dtype=np.float64).reshape(-1)[:3]])
+    eng.lib.check(eng.lib.dll.lk_normals(knn.h, ptr(pos), N, C.c_float(radius), cam, ptr(normals), ptr(valid), eng.stream), 'lk_normals')
+    if own:
+        if eng.device.type == 'cuda':
+            torch.cuda.current_stream(eng.device).synchronize()
+        knn.close()
+    return normals, valid
+
+
+def icp_sums(eng, tgt, src_pos, T, max_dist, tukey_k=0.0, mode=_ffi.ICP_POINT_TO_PLANE, want_corr=False):
+    """One lk_icp_accumulate call: (sums float64 [32] on the host, correspondence index [P] int32 on the device or None).
+    tgt: SegmentCloud; T: 4 x 4 (rounded to fp32 for the device)."""
+    src_pos = src_pos.contiguous()
+    P = int(src_pos.shape[0])
+    T12 = (C.c_float * 12)(*np.asarray(T, dtype=np.float64)[:3, :4].astype(np.float32).ravel().tolist())
+    n_scr = int(eng.lib.dll.lk_icp_scratch_floats(P))
+    scratch = eng.empty(max(n_scr, 1))
+    out = eng.zeros(_ffi.ICP_SUMS, dtype=torch.float64)
+    corr = eng.empty(P, dtype=torch.int32) if want_corr else None
+    p2p = mode == _ffi.ICP_POINT_TO_PLANE
+    nrm, val = tgt.normals if p2p else (None, None)
+    eng.lib.check(eng.lib.dll.lk_icp_accumulate(tgt.knn.h, ptr(tgt.pos), ptr(nrm), ptr(val), ptr(src_pos), P, T12, C.c_float(max_dist),
+                                                C.c_float(tukey_k), int(mode), ptr(corr), ptr(scratch), n_scr, ptr(out), eng.stream),
+                  'lk_icp_accumulate')
+    return out.cpu().numpy(), corr           # the copy is the one synchronisation of an iteration
+
+
+def unpack_sums(s):
+    """(A 6 x 6 symmetric, b [6], count, sum_d2, sum_w_r2) of a row of lk_icp_accumulate sums."""
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = s[:21]
+    A = A + np.triu(A, 1).T
+    return A, np.array(s[21:27]), float(s[27]), float(s[28]), float(s[29])
+
+
+def icp(eng, src, tgt, init=None, max_dist=FINE_DIST, tukey_k=0.0, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+    """Point-to-plane ICP of src onto tgt (SegmentClouds) from the 4 x 4 `init`: Gauss-Newton, sums on the device, the 6 x 6 solve
+    in fp64 here, T <- exp(x) T; Open3D's default convergence criteria (the change of fitness and of inlier rmse both below 1e-6, or 30
+    iterations).  Returns dict(T, fitness = count / P, inlier_rmse = sqrt(sum d2 / count), iterations).  count is the number of
+    correspondences that enter the sums: those within max_dist whose target normal is valid."""
+    T = np.eye(4) if init is None else np.array(init, dtype=np.float64)
+    P = max(len(src), 1)
+
+    def evaluate(T):
+        s, _ = icp_sums(eng, tgt, src.pos, T, max_dist, tukey_k)
+        A, b, cnt, sd2, _ = unpack_sums(s)
+        return A, b, cnt / P, (np.sqrt(sd2 / cnt) if cnt > 0 else 0.0), cnt
+
+    A, b, fit, rmse, cnt = evaluate(T)
+    it = 0
+    for it in range(1, max_iter + 1):
+        if cnt < 6:
+            break
+        try:
+            x = np.linalg.solve(A, -b)
+        except np.linalg.LinAlgError:
+            break
+        T = se3_exp(x) @ T
+        A, b, fit_new, rmse_new, cnt = evaluate(T)
+        done = abs(fit_new - fit) < rel_fitness and abs(rmse_new - rmse) < rel_rmse
+        fit, rmse = fit_new, rmse_new
+        if done:
+            break
+    return {'T': T, 'fitness': fit, 'inlier_rmse': rmse, 'iterations': it}
+
+
+def information_matrix(eng, src, tgt, T, max_dist=FINE_DIST):
+    """sum G^T G over the correspondences within max_dist at T, G = [-[q]x | I] (Open3D's get_information_matrix_from_point_clouds):
+    (6 x 6, count, sum d2)."""
+    s, _ = icp_sums(eng, tgt, src.pos, T, max_dist, mode=_ffi.ICP_INFORMATION)
+    A, _, cnt, sd2, _ = unpack_sums(s)
+    return A, cnt, sd2
+
+
+def register_pair(seg_s, seg_t, method='robust_icp', adjacent=False, eng=None):
+    """src/common.py pairwise_registration + register_point_cloud_pair for two SegmentClouds, starting from the identity.
+    'identity': the odometry edge of adjacent segments; 'icp': coarse 0.3 m then fine 0.03 m; 'robust_icp': coarse 0.3 m plain, then
+    fine 0.03 m with the Tukey loss k = 0.01.  A non-adjacent pair whose transform stays the identity or whose overlap
+    information[5,5] / n_points is below 0.3 fails: identity transform, identity information."""
+    if method not in METHODS:
+        raise NotImplementedError(f'loop_closure.method {method!r}: one of {METHODS}')
+    eng = eng if eng is not None else seg_s.eng
+    out = {'fitness': 0.0, 'inlier_rmse': 0.0, 'iterations': 0}
+    if method == 'identity':
+        T = np.eye(4)
+    else:
+        coarse = icp(eng, seg_s, seg_t, np.eye(4), COARSE_DIST)
+        fine = icp(eng, seg_s, seg_t, coarse['T'], FINE_DIST, TUKEY_K if method == 'robust_icp' else 0.0)
+        T = fine['T']
+        out.update(fitness=fine['fitness'], inlier_rmse=fine['inlier_rmse'], iterations=coarse['iterations'] + fine['iterations'],
+                   T_coarse=coarse['T'])
+    info, cnt, sd2 = information_matrix(eng, seg_s, seg_t, T, FINE_DIST)
+    n_points = max(min(len(seg_s), len(seg_t)), 1)
+    out.update(T=T, information=info, n_points=n_points, overlap=info[5, 5] / n_points, success=True,
+               transl_mag=float(np.abs(T[:3, 3]).mean()))
+    if method == 'identity':
+        out.update(fitness=cnt / max(len(seg_s), 1), inlier_rmse=float(np.sqrt(sd2 / cnt)) if cnt > 0 else 0.0)
+    if not adjacent and (np.trace(T) == 4.0 or out['overlap'] < 0.3):
+        out.update(success=False, T=np.eye(4), information=np.eye(6))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ pose graph (host, fp64)
+def line_process_mu(edges, lc_pref, max_dist):
+    """The line-process scale of Open3D's global_optimization: lc_pref x max_dist^2 x (mean over the edges of information[5,5],
+    the number of correspondences) - the energy e^T Lambda e of an edge all of whose correspondences are sqrt(lc_pref) x max_dist off."""
+    if not edges:
+        return 0.0
+    return float(lc_pref) * float(max_dist) ** 2 * float(np.mean([np.asarray(e[3])[5, 5] for e in edges]))
+
+
+def _lm(n_nodes, edges, X, mu, max_iter=100):
+    """Levenberg-Marquardt over X_1 .. X_{n-1} (left perturbations X <- exp(d) X, node 0 fixed) of
+    sum_certain x + sum_uncertain mu x / (mu + x), x = e^T Lambda e, e = log(T_st^-1 X_t^-1 X_s): the Geman-McClure form that
+    Choi et al.'s line process l = (mu / (mu + x))^2 minimises to; l is also the weight of the edge's Gauss-Newton terms."""
+    def residuals(X):
+        out = []
+        for s, t, T, L, unc in edges:
+            A = _inv(T) @ _inv(X[t])
+            e = se3_log(A @ X[s])
+            out.append((A, e, float(e @ L @ e)))
+        return out
+
+    def cost(res):
+        return sum((mu * x / (mu + x) if (unc and mu > 0) else x) for (_, _, x), (_, _, _, _, unc) in zip(res, edges))
+
+    def weights(res):
+        return [((mu / (mu + x)) ** 2 if (unc and mu > 0) else 1.0) for (_, _, x), (_, _, _, _, unc) in zip(res, edges)]
+
+    res = residuals(X)
+    c, lam = cost(res), 1e-6
+    nv = 6 * (n_nodes - 1)
+    for _ in range(max_iter):
+        if nv == 0:
+            break
+        H, g = np.zeros((nv, nv)), np.zeros(nv)
+        for (A, e, x), (s, t, T, L, unc), l in zip(res, edges, weights(res)):
+            w, v = e[:3], e[3:]
+            ad = np.zeros((6, 6))
+            ad[:3, :3] = _hat(w); ad[3:, 3:] = _hat(w); ad[3:, :3] = _hat(v)
+            J = (np.eye(6) - 0.5 * ad + ad @ ad / 12.0) @ _adjoint(A)        # d e / d (delta_s - delta_t), left Jacobian inverse to 2nd order
+            for (a, sa) in ((s, 1.0), (t, -1.0)):
+                if a == 0:
+                    continue
+                ia = slice(6 * (a - 1), 6 * a)
+                g[ia] += l * sa * (J.T @ L @ e)
+                for (b, sb) in ((s, 1.0), (t, -1.0)):
+                    if b == 0:
+                        continue
+                    H[ia, slice(6 * (b - 1), 6 * b)] += l * sa * sb * (J.T @ L @ J)
+        step_ok = False
+        for _try in range(30):
+            try:
+                d = np.linalg.solve(H + lam * (np.diag(np.diag(H)) + 1e-12 * np.eye(nv)), -g)
+            except np.linalg.LinAlgError:
+                lam *= 10.0
+                continue
+            Xn = [X[0]] + [se3_exp(d[6 * (i - 1):6 * i]) @ X[i] for i in range(1, n_nodes)]
+            rn = residuals(Xn)
+            cn = cost(rn)
+            if cn <= c:
+                step_ok = True
+                break
+            lam *= 10.0
+        if not step_ok:
+            break
+        X, res, lam = Xn, rn, max(lam / 10.0, 1e-12)
+        small = np.abs(d).max() < 1e-13 or cn < 1e-26
+        c = cn
+        if small:
+            break
+    return X, weights(res), c
+
+
+def optimize_pose_graph(n_nodes, edges, prune=0.25, lc_pref=5.0, max_dist=FINE_DIST, max_iter=100):
+    """Open3D's global_optimization for the segment graph.  edges: (s, t, T_st 4 x 4, Lambda_st 6 x 6, uncertain); T_st moves the
+    points of segment s onto segment t, so the corrections X_i (node 0 fixed to the identity) are sought with T_st = X_t^-1 X_s.
+    Uncertain (loop) edges carry a line-process weight; those ending below `prune` are dropped and the graph is optimised again.
+    Returns dict(nodes [n,4,4], weights (per input edge, at the end of the first pass), kept (mask), mu, cost)."""
+    edges = [(int(s), int(t), np.asarray(T, dtype=np.float64), np.asarray(L, dtype=np.float64), bool(u)) for s, t, T, L, u in edges]
+    mu = line_process_mu(edges, lc_pref, max_dist)
+    X = [np.eye(4) for _ in range(n_nodes)]
+    X, w, c = _lm(n_nodes, edges, X, mu, max_iter)
+    kept = [(not e[4]) or wi >= prune for e, wi in zip(edges, w)]
+    if not all(kept):
+        # the second pass keeps the surviving edges' line process on, as Open3D's second global_optimization pass does
+        X, _, c = _lm(n_nodes, [e for e, k in zip(edges, kept) if k], X, mu, max_iter)
+    return {'nodes': np.stack(X), 'weights': np.array(w), 'kept': np.array(kept), 'mu': mu, 'cost': c}
+
+
+# ------------------------------------------------------------------------------------------------ the closer
+DEFAULTS = {'enabled': False, 'method': 'robust_icp', 'candidates': 'pose', 'max_center_dist': 1.5, 'min_axis_cos': 0.5}
+
+
+def settings(cfg):
+    """cfg['loop_closure'] over the defaults (absent key: disabled)."""
+    out = dict(DEFAULTS)
+    out.update(cfg.get('loop_closure') or {})
+    return out
+
+
+class LoopCloser:
+    """Owns the per-point segment id of a NeuralPointCloud and runs a closure when a segment opens (slam.Mapper calls on_new_segment)."""
+
+    def __init__(self, cfg, npc, slam=None):
+        lc = settings(cfg)
+        dist = getattr(slam, 'dist', None)
+        if dist is not None and getattr(dist, 'world', 1) > 1:
+            raise NotImplementedError('loop_closure.enabled with world > 1: rank 0 would decide and broadcast the corrections '
+                                      '(SURVEY.md 8(e)); that exchange is not built - run loop closure on one rank')
+        if lc['method'] not in METHODS:
+            raise NotImplementedError(f"loop_closure.method {lc['method']!r}: one of {METHODS}")
+        tr = cfg.get('tracking', {})
+        self.cfg, self.npc, self.slam, self.eng = lc, npc, slam, npc.eng
+        self.method, self.candidates = lc['method'], lc['candidates']
+        self.min_dist = tr.get('min_dist', 1)
+        self.prune_pgo, self.lc_pref = tr.get('prune_pgo', 0.25), tr.get('lc_pref', 5.0)
+        self.fitness_thresh, self.std_threshold = tr.get('fitness_thresh', 0.1), tr.get('std_threshold', 0.04)
+        self.trans_mag_percentile = tr.get('trans_mag_percentile', 90)
+        self.current_segment = 0
+        self.loop_edges = []             # accepted loop edges of earlier closures, kept in the corrected frames
+        self.odometry_info = {}          # (s, s + 1) -> information at the identity
+        self.corrections = []            # per segment: the accumulated 4 x 4 correction (checkpoint 'fragments')
+        self.last_edges, self.last_result, self.last_registrations = None, None, []
+        npc.closer = self
+        npc._seg = torch.zeros(npc.capacity, dtype=torch.int32, device=self.eng.device)
+
+    # ---- bookkeeping
+    def segment_rows(self, i):
+        return torch.nonzero(self.npc._seg[:self.npc.n] == i).reshape(-1)
+
+    def segment_cloud(self, i, segments):
+        return SegmentCloud(self.eng, self.npc._pos[:self.npc.n][self.segment_rows(i)], segments[i]['est_c2w'][:3, 3])
+
+    def pose_candidates(self, segments):
+        """Pairs (newest, t): non-adjacent by more than tracking.min_dist, keyframe centres within max_center_dist metres and
+        optical axes within min_axis_cos."""
+        s = len(segments) - 1
+        ks = segments[s]['est_c2w'].detach().cpu().double()
+        out = []
+        for t in range(s):
+            if abs(s - t) <= self.min_dist:
+                continue
+            kt = segments[t]['est_c2w'].detach().cpu().double()
+            if float((ks[:3, 3] - kt[:3, 3]).norm()) <= self.cfg['max_center_dist'] and \
+                    float(torch.dot(ks[:3, 2], kt[:3, 2])) >= self.cfg['min_axis_cos']:
+                out.append((s, t))
+        return out
+
+    def filter_edges(self, regs):
+        """The reference's old_trans_mag_filter branch: if the translation magnitudes of the successful loop registrations spread by no
+        more than tracking.std_threshold all of them are kept; otherwise those below their trans_mag_percentile-th percentile with a
+        fitness of at least tracking.fitness_thresh."""
+        ok = [r for r in regs if r['success']]
+        if not ok:
+            return []
+        mags = np.array([r['transl_mag'] for r in ok])
+        if mags.std() <= self.std_threshold:
+            return ok
+        thr = np.percentile(mags, self.trans_mag_percentile)
+        return [r for r in ok if r['transl_mag'] < thr and r['fitness'] >= self.fitness_thresh]
+
+    # ---- one closure
+    def compute_correction(self, segments):
+        """Register the candidate pairs of the newest segment and optimise the pose graph.  Returns the optimize_pose_graph result,
+        or None when the newest segment got no loop edge (nothing is optimised then, as in the reference)."""
+        n = len(segments)
+        self.last_edges, self.last_result, self.last_registrations = None, None, []
+        if n < 3:
+            return None
+        pairs = self.candidates(segments) if callable(self.candidates) else self.pose_candidates(segments)
+        pairs = [(int(s), int(t)) for s, t in pairs]
+        if not pairs:
+            return None
+        clouds = {}
+
+        def cloud(i):
+            if i not in clouds:
+                clouds[i] = self.segment_cloud(i, segments)
+            return clouds[i]
+
+        try:
+            regs = []
+            for s, t in pairs:
+                r = register_pair(cloud(s), cloud(t), self.method, adjacent=False, eng=self.eng)
+                r.update(s=s, t=t)
+                regs.append(r)
+            self.last_registrations = regs
+            new_loops = [(r['s'], r['t'], r['T'], r['information'], True) for r in self.filter_edges(regs)]
+            if not any(n - 1 in (e[0], e[1]) for e in new_loops):
+                return None
+            for i in range(n - 1):
+                if (i, i + 1) not in self.odometry_info:
+                    self.odometry_info[(i, i + 1)] = register_pair(cloud(i), cloud(i + 1), 'identity', adjacent=True, eng=self.eng)['information']
+        finally:
+            if self.eng.device.type == 'cuda':
+                torch.cuda.current_stream(self.eng.device).synchronize()
+            for c in clouds.values():
+                c.close()
+        edges = [(i, i + 1, np.eye(4), self.odometry_info[(i, i + 1)], False) for i in range(n - 1)] + self.loop_edges + new_loops
+        self.last_edges = edges
+        self.last_result = optimize_pose_graph(n, edges, prune=self.prune_pgo, lc_pref=self.lc_pref, max_dist=FINE_DIST)
+        return self.last_result
+
+    def apply(self, pose_graph, segments, estimate_c2w_list=None, keyframe_dict=None, n_frames=None):
+        """Move the map by the node matrices: positions (lk_apply_correction), the frame poses of every segment, the segments' and the
+        keyframes' poses, then rebuild the neighbour index."""
+        nodes = np.asarray(pose_graph['nodes'] if isinstance(pose_graph, dict) else pose_graph, dtype=np.float64)
+        n, npc, eng = len(segments), self.npc, self.eng
+        assert nodes.shape[0] == n
+        mats = torch.from_numpy(nodes[:, :3, :4].astype(np.float32).reshape(n, 12)).to(eng.device).contiguous()
+        eng.lib.check(eng.lib.dll.lk_apply_correction(ptr(npc._pos), npc.n, ptr(npc._seg), ptr(mats), n, eng.stream), 'lk_apply_correction')
+        if npc.n:
+            npc.knn.build(npc._pos[:npc.n])
+        starts = [int(sg['idx']) for sg in segments]
+
+        def moved(X, c2w):
+            # 4 x 4 algebra on the host in fp64, rounded once: the same bits wherever the pose lives
+            out = torch.from_numpy(X) @ c2w.detach().cpu().double()
+            out[3, :] = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)
+            return out.to(c2w.dtype).to(c2w.device)
+
+        def seg_of(frame):
+            return max(int(np.searchsorted(starts, int(frame), side='right')) - 1, 0)
+
+        if estimate_c2w_list is not None:
+            end_all = len(estimate_c2w_list) if n_frames is None else n_frames
+            for i in range(n):
+                a, b = starts[i], (starts[i + 1] if i + 1 < n else end_all)
+                if i == 0:
+                    a = 0
+                for f in range(a, b):
+                    estimate_c2w_list[f] = moved(nodes[i], estimate_c2w_list[f])
+        for i, sg in enumerate(segments):
+            sg['est_c2w'] = moved(nodes[i], sg['est_c2w'])
+        for kf in (keyframe_dict or []):
+            kf['est_c2w'] = moved(nodes[seg_of(kf['idx'])], kf['est_c2w'])
+        # remembered loop edges follow their segments: T' = X_t T X_s^-1
+        kept = pose_graph['kept'] if isinstance(pose_graph, dict) and self.last_edges is not None else None
+        if kept is not None:
+            self.loop_edges = [(s, t, nodes[t] @ T @ _inv(nodes[s]), L, True)
+                               for (s, t, T, L, u), k in zip(self.last_edges, kept) if u and k]
+        while len(self.corrections) < n:
+            self.corrections.append(np.eye(4))
+        self.corrections = [nodes[i] @ self.corrections[i] for i in range(n)]
+
+    def on_new_segment(self, mapper, first_new_row):
+        """slam.Mapper: segment len(segments) - 1 has just opened; the rows the opening frame inserted belong to it."""
+        segments = mapper.segments
+        self.current_segment = len(segments) - 1
+        self.npc._seg[first_new_row:self.npc.n] = self.current_segment
+        pg = self.compute_correction(segments)
+        if pg is None:
+            return None
+        slam = self.slam
+        self.apply(pg, segments, slam.estimate_c2w_list if slam is not None else None, mapper.keyframe_dict,
+                   n_frames=int(segments[-1]['idx']) + 1)
+        return pg
+
+    def fragments(self, segments):
+        """The checkpoint's per-segment records."""
+        out = []
+        for i, sg in enumerate(segments):
+            out.append({'start_idx': int(sg['idx']), 'keyframe': sg['est_c2w'].detach().cpu(),
+                        'n_points': int((self.npc._seg[:self.npc.n] == i).sum()),
+                        'correction': torch.from_numpy(self.corrections[i] if i < len(self.corrections) else np.eye(4))})
+        return out

@@ -1,15 +1,16 @@
 """Drop-in host classes with the reference's names and call signatures for the render/optimise path:
 
   NICER             src/conv_onet/models/decoder.py:549-626   (weights container + state_dict, forward)
-  NeuralPointCloud  src/neural_point.py:29-124, 1252-1708     (query/store half; one segment, no loop closure)
+  NeuralPointCloud  src/neural_point.py:29-124, 1252-1708     (query/store half; per-point segment ids when loop closure is on)
   Renderer          src/utils/Renderer.py:6-276               (render_batch_ray, render_img)
   Mapper            src/Mapper.py:35-1049                     (optimize_map; map_frame = one pass of run()'s body)
   Tracker           src/Tracker.py:29-427                     (optimize_cam_in_batch; track_frame = run()'s body)
   Point_SLAM        src/Point_SLAM.py:37-252                  (single-process orchestration)
 
 All arithmetic of the hot path runs in libloopyhip (loopy_slam_amd.core / .steps / .optim); what remains here is
-per-frame bookkeeping in torch.  Out of scope: loop closure / fragments, datasets, meshing,
-visualisation.  Every class takes an optional `eng` (core.Engine);
+per-frame bookkeeping in torch.  Loop closure's geometric back end (segment registration, pose graph, map correction) is
+loop_closure.py, off by default (cfg['loop_closure']['enabled']); place recognition stays out of scope, as do datasets, meshing and
+visualisation (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
 the default is the gfx950 library on the current CUDA device.
 """
 import math
@@ -19,7 +20,7 @@ import types
 import numpy as np
 import torch
 
-from . import _ffi, core, optim, parallel, steps, synthetic
+from . import _ffi, core, loop_closure, optim, parallel, steps, synthetic
 from .common import get_camera_from_tensor, get_tensor_from_camera, get_rays, get_samples, get_rays_from_uv
 
 
@@ -191,6 +192,9 @@ class NeuralPointCloud:
         self._cell = max(pc['radius_query'], 1e-3)
         # feature initialisation draws on the device (Philox): no host RNG + upload per insertion
         self._gen = torch.Generator(device=self.eng.device).manual_seed(cfg.get('setup_seed', 1219))
+        # loop closure (loop_closure.LoopCloser attaches itself): the closer and the segment id of every row, one int32 beside _pos.
+        # Both stay None with the feature off - nothing is allocated and nothing is called
+        self.closer, self._seg = None, None
         self._alloc(capacity)
         self.n = 0
         self._input_pos, self._input_rgb = [], []
@@ -209,6 +213,10 @@ class NeuralPointCloud:
         self._alloc(max(need, 2 * self.capacity))
         for new, o in zip((self._pos, self._geo, self._col), old):
             new[:self.n] = o[:self.n]
+        if self._seg is not None:
+            seg = torch.zeros(self.capacity, dtype=torch.int32, device=self.eng.device)
+            seg[:self.n] = self._seg[:self.n]
+            self._seg = seg
         if self.n:
             self.knn.build(self._pos[:self.n])
 
@@ -309,12 +317,25 @@ class NeuralPointCloud:
         if k:
             self._grow(self.n + k)
             self._pos[self.n:self.n + k] = pts
+            if self._seg is not None:
+                self._seg[self.n:self.n + k] = self.closer.current_segment
             # neural_point.py:1608-1614: normal(0, 0.1) features for the new points
             self._geo[self.n:self.n + k] = (torch.randn(k, 32, generator=self._gen, device=self.eng.device) * 0.1).to(self.feat_dtype)
             self._col[self.n:self.n + k] = (torch.randn(k, 32, generator=self._gen, device=self.eng.device) * 0.1).to(self.feat_dtype)
             self.n += k
             self.knn.build(self._pos[:self.n])             # counting-sort rebuild on the device (no IVF re-training)
         return n_acc
+
+    # ---- loop closure (neural_point.py:144-215, 585-990): the reference's names, forwarded to the closer
+    def compute_correction(self, segments):
+        if self.closer is None:
+            raise RuntimeError("loop closure is off: set cfg['loop_closure']['enabled']")
+        return self.closer.compute_correction(segments)
+
+    def apply_correction(self, pose_graph, segments, estimate_c2w_list=None, keyframe_dict=None, n_frames=None):
+        if self.closer is None:
+            raise RuntimeError("loop closure is off: set cfg['loop_closure']['enabled']")
+        return self.closer.apply(pose_graph, segments, estimate_c2w_list, keyframe_dict, n_frames)
 
 
 # ============================================================================================ Renderer
@@ -452,14 +473,17 @@ class Mapper:
         self.last_add_counts, self.last_frame_pts_add, self.last_num_joint_iters = [], 0, 0
         self.use_dynamic_radius = cfg['use_dynamic_radius']
         self.keyframe_list, self.keyframe_dict = [], []
-        # SEGMENTS (the reference's map fragments, neural_point.py:1300-1326): the loop-closure machinery that owns them is out of scope,
-        # but the end-of-sequence refinement optimises over ONE KEYFRAME PER SEGMENT (Mapper.py:386-396, neural_point.py:1424-1433) - so
+        # SEGMENTS (the reference's map fragments, neural_point.py:1300-1326): loop closure registers them against each other when it is on
+        # (self.closer below), and the end-of-sequence refinement optimises over ONE KEYFRAME PER SEGMENT (Mapper.py:386-396, neural_point.py:1424-1433) - so
         # the segmentation of the trajectory is kept: a segment starts at frame 0 and at every mapped frame whose tracked pose has left the
         # last segment's keyframe pose by more than segment_rel_trans metres or whose optical axis makes a cosine below segment_rot_cos
         # with it (segment_strategy 'rot_trans'; 'fixed': every fixed_segment_size frames).  `segments` is a plain list of
-        # {idx, color, depth, est_c2w, r2_query, exposure_feat} records: a caller that runs its own segmentation (a loop-closure module)
-        # may replace or extend it before the last frame is mapped
+        # {idx, color, depth, est_c2w, r2_query, exposure_feat} records: a caller that runs its own segmentation may replace or extend it
+        # before the last frame is mapped
         self.segments = []
+        # loop closure (loop_closure.py; off unless cfg['loop_closure']['enabled']): when a segment opens, its candidate pairs are registered,
+        # the segment pose graph is optimised and map, poses and keyframes are moved - where the reference calls apply_transformation
+        self.closer = loop_closure.LoopCloser(cfg, self.npc, slam) if loop_closure.settings(cfg)['enabled'] else None
         self.segment_strategy = m.get('segment_strategy', 'rot_trans')
         self.segment_rot_cos, self.segment_rel_trans = m.get('segment_rot_cos', 0.94), m.get('segment_rel_trans', 0.30)
         self.fixed_segment_size = m.get('fixed_segment_size', 50)
@@ -705,6 +729,7 @@ class Mapper:
         cur_c2w = cur_c2w if cur_c2w is not None else slam.estimate_c2w_list[idx].to(self.eng.device)
         init = idx == 0
         last = idx == slam.n_img - 1
+        rows_before = self.npc.n
         color_refine = bool(last and self.color_refine and not init)
         num_joint_iters, outer = (self.iters_first if init else self.num_joint_iters), 1
         saved = None
@@ -741,6 +766,8 @@ class Mapper:
             self.segments.append({'idx': idx, 'color': gt_color, 'depth': gt_depth, 'est_c2w': cur_c2w.clone(), 'gt_c2w': gt_c2w,
                                   'r2_query': getattr(self, 'cur_r2_query', None),
                                   'exposure_feat': self.cur_exposure_feat.detach() if self.slam.encode_exposure else None})
+            if self.closer is not None and self.closer.on_new_segment(self, rows_before) is not None:
+                cur_c2w = self.segments[-1]['est_c2w'].clone()          # the corrected pose: the tracker starts the next frame from it
         self.prev_c2w = cur_c2w.clone()         # Mapper.py:1001
         slam.mapping_idx[0] = idx
         return self.last_log
@@ -1032,7 +1059,7 @@ class Logger:
             'keyframe_dict': [{k: cpu(v) for k, v in kf.items()} for kf in keyframe_dict],
             'selected_keyframes': selected_keyframes if selected_keyframes is not None else {},
             'idx': idx,
-            'fragments': [],
+            'fragments': self.mapper.closer.fragments(self.mapper.segments) if getattr(self.mapper, 'closer', None) is not None else [],
             'exposure_feat_all': torch.stack([cpu(e) for e in exposure_feat], dim=0) if exposure_feat else None,
         }
         if last_log:
