@@ -565,6 +565,67 @@ int lk_icp_accumulate(lk_knn_t tgt, const float* tgt_pos, const float* tgt_norma
  * The neighbour index is stale afterwards: lk_knn_build. */
 int lk_apply_correction(float* pos, int64_t N, const int32_t* seg_id, const float* mats, int32_t n_seg, void* stream);
 
+/* ---------------------------------------------------------------- loop closure: global start (FPFH + RANSAC)
+ * What the reference's default "robust_icp" runs before its ICP (src/common.py: preprocess_point_cloud, execute_global_registration around
+ * Open3D).  fp32 throughout, no floating-point atomics, every sum in an order fixed by the inputs: equal inputs and seed give equal bits.
+ *
+ * Voxel downsample.  lk_voxel_keys: key[i] = (kx << 42) | (ky << 21) | kz with k = clamp(floor((p - origin) / voxel), 0, LK_VOXEL_AXIS_MAX) per
+ * axis, the subtraction and the division each rounded once (host_origin3: HOST pointer; the caller passes min - 0.5 voxel).  The caller sorts
+ * the keys (stable) and passes the sorted keys to lk_voxel_heads (head[i] = 1 where a voxel's run begins), compacts the heads (lk_compact_large)
+ * into `starts`, and lk_voxel_downsample writes one centroid per voxel, in ascending key order: the points order[starts[j]] .. of the run are
+ * summed in that order relative to the first of them, divided by their number and added back to it. */
+#define LK_VOXEL_AXIS_MAX 2097151
+int lk_voxel_keys(const float* pos, int64_t N, const float* host_origin3, float voxel, int64_t* out_keys, void* stream);
+int lk_voxel_heads(const int64_t* sorted_keys, int64_t N, uint8_t* out_head, void* stream);
+int lk_voxel_downsample(const float* pos, int64_t N, const int64_t* order /*[N] point of each sorted key*/, const int32_t* starts /*[n_vox]*/,
+                        int32_t n_vox, float* out_centroids /*[n_vox,3]*/, void* stream);
+/* Re-orders the points inside every cell of a built index by ascending point index.  lk_knn_build leaves them in the order its counting
+ * atomics landed; afterwards every walk over the index (lk_normals, lk_fpfh) meets the points in an order the cloud alone fixes, so its
+ * floating-point sums have the same bits after every rebuild.  Query results do not change. */
+int lk_knn_canonicalize(lk_knn_t knn, void* stream);
+/* FPFH (Rusu et al. 2009) with Open3D's conventions over ALL indexed points k != i with contract d2 <= radius^2 and a valid normal (Open3D
+ * stops at the 100 nearest).  Pair features of (p1 = point i, n1) and (p2 = neighbour, n2): e = p2 - p1, d = |e|, a1 = n1.e / d, a2 = n2.e / d;
+ * if |n1.e| < |n2.e| (acos|a1| > acos|a2|; this one comparison in fp64 on the exact differences - ties are common: a neighbour along the
+ * normal - and they flip the sign of f2) the roles swap: u = n2, m = n1, e = -e, f2 = -a2, else u = n1, m = n2, f2 = a1;
+ * v = (e x u) / |e x u|, w = u x v, f1 = v.m, f0 = atan2(w.m, u.m); d = 0 or |e x u| = 0: f0 = f1 = f2 = 0.
+ * Bins: clamp(floor(11 (f0 + pi) / (2 pi)), 0, 10), 11 + clamp(floor(11 (f1 + 1) / 2), 0, 10), 22 + clamp(floor(11 (f2 + 1) / 2), 0, 10);
+ * out_spfh[i][bin] = (pairs in the bin) x (100 / number of neighbours).
+ * out_fpfh[i][b] = scale[b / 11] x (sum over the neighbours with d2 > 0 of out_spfh[k][b] / d2) + out_spfh[i][b], scale = 100 / (the sum of
+ * the block's 11 neighbour sums), 0 for a zero block.  The neighbour sums follow the canonical cell order (lk_knn_canonicalize).
+ * A point with valid[i] = 0 gets zero rows and is nobody's neighbour. */
+#define LK_FPFH_DIM 33
+int lk_fpfh(lk_knn_t knn, const float* pos, const float* normals, const uint8_t* valid, int64_t N, float radius,
+            float* out_spfh /*[N,33]*/, float* out_fpfh /*[N,33]*/, void* stream);
+/* For every row i of A[Na,33]: out_idx[i] = the row j of B[Nb,33] with the smallest (d2, j), d2 = sum over the 33 columns ascending of
+ * (A[i][c] - B[j][c])^2 (each term rounded, added one by one), out_d2[i] = that d2.  Rows with validB[j] = 0 are never chosen; a row with
+ * validA[i] = 0, or without a candidate, gets -1 and 0.  The masks may be NULL (all valid). */
+int lk_feature_match(const float* A, const uint8_t* validA, int64_t Na, const float* B, const uint8_t* validB, int64_t Nb,
+                     int32_t* out_idx, float* out_d2, void* stream);
+/* RANSAC over M correspondences corr[M][2] = (source point, target point); lk_ransac_gather copies their points into cs[M,3] / ct[M,3].
+ * lk_ransac_hypotheses, trial t = trial0 + (0 .. n_trials): (r0, r1, r2, r3) = Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (t & 0xffffffff, t >> 32, 0, 0) - ten rounds of
+ *     (c0, c1, c2, c3) <- (hi(0xCD9E8D57 c2) ^ c1 ^ k0, lo(0xCD9E8D57 c2), hi(0xD2511F53 c0) ^ c3 ^ k1, lo(0xD2511F53 c0)),
+ *     then (k0, k1) += (0x9E3779B9, 0xBB67AE85)
+ * - and the three correspondences are i_k = (r_k x M) >> 32, k = 0, 1, 2 (out_triples[n_trials,3], may be NULL).  The trial is dropped when two
+ * indices are equal, when for one of the sides (0,1), (1,2), (2,0) |s_a - s_b| < edge_ratio |t_a - t_b| or the other way round, or when after
+ * the rigid least-squares fit of the three pairs (Horn's unit quaternion by cyclic Jacobi, no scale, det = +1; this fit alone runs in fp64 and is rounded to fp32: a thin triangle loses
+ * the rotation about its long side in fp32) one of the three points lies
+ * more than dist_thr from its partner.  out_ok[n_trials] = 1 for a survivor, out_T[n_trials,12] its row-major 3 x 4 transform (zeros else).
+ * lk_ransac_score: for hypothesis h < *n_survivors (device), transform out_T[survivors[h]]: out_count[h] = number of correspondences with
+ * d2(T s, t) <= dist_thr^2 (the points moved by three fused multiply-adds per coordinate as in lk_icp_accumulate), out_sum_d2[h] = their d2
+ * summed per lane of a 64-lane wave over j = lane, lane + 64, .. and then by an xor butterfly (1, 2, .., 32).
+ * lk_ransac_best folds the batch into best[LK_RANSAC_BEST] (int32, device; set best[0] = -1 and the rest 0 before the first batch):
+ * [0] count, [1] bits of sum d2, [2] / [3] trial low / high, [4..15] bits of the transform, [16] survivors so far.  Order: count descending,
+ * sum d2 ascending, trial ascending. */
+#define LK_RANSAC_BEST 20
+int lk_ransac_gather(const float* src, const float* tgt, const int32_t* corr, int32_t M, float* out_cs, float* out_ct, void* stream);
+int lk_ransac_hypotheses(const float* cs, const float* ct, int32_t M, uint64_t seed, uint64_t trial0, int32_t n_trials, float edge_ratio,
+                         float dist_thr, int32_t* out_triples, uint8_t* out_ok, float* out_T, void* stream);
+int lk_ransac_score(const float* cs, const float* ct, int32_t M, const float* T_all, const int32_t* survivors, const int32_t* n_survivors,
+                    int32_t max_survivors, float dist_thr, int32_t* out_count, float* out_sum_d2, void* stream);
+int lk_ransac_best(const int32_t* count, const float* sum_d2, const int32_t* survivors, const int32_t* n_survivors, const float* T_all,
+                   uint64_t trial0, int32_t* best, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

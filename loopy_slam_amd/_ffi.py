@@ -37,6 +37,7 @@ ERR_RANGE = -4
 
 EXPOSURE_MAX_F = 32
 ICP_POINT_TO_PLANE, ICP_INFORMATION, ICP_SUMS = 0, 1, 32
+FPFH_DIM, RANSAC_BEST = 33, 20
 ADAM_MAX_SEG = 16
 
 _fp = C.c_void_p     # every device pointer crosses the ABI as an integer address
@@ -214,6 +215,17 @@ class LoopyLib:
             ('lk_icp_accumulate', [C.c_void_p, _fp, _fp, _fp, _fp, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, _fp,
                                    _fp, C.c_int64, _fp, C.c_void_p], C.c_int),
             ('lk_apply_correction', [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_void_p], C.c_int),
+            ('lk_voxel_keys', [_fp, C.c_int64, C.POINTER(C.c_float), C.c_float, _fp, C.c_void_p], C.c_int),
+            ('lk_voxel_heads', [_fp, C.c_int64, _fp, C.c_void_p], C.c_int),
+            ('lk_voxel_downsample', [_fp, C.c_int64, _fp, _fp, C.c_int32, _fp, C.c_void_p], C.c_int),
+            ('lk_knn_canonicalize', [C.c_void_p, C.c_void_p], C.c_int),
+            ('lk_fpfh', [C.c_void_p, _fp, _fp, _fp, C.c_int64, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_feature_match', [_fp, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_ransac_gather', [_fp, _fp, _fp, C.c_int32, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_ransac_hypotheses', [_fp, _fp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_float, C.c_float, _fp, _fp, _fp,
+                                      C.c_void_p], C.c_int),
+            ('lk_ransac_score', [_fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_ransac_best', [_fp, _fp, _fp, _fp, _fp, C.c_uint64, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

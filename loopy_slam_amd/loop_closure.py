@@ -8,10 +8,14 @@ Reference                                                  here
   o3d global_optimization (Levenberg-Marquardt)            optimize_pose_graph (host, fp64)
   src/neural_point.py  apply_correction / apply_transformation   LoopCloser.apply -> lk_apply_correction + lk_knn_build
 
-Out of scope: place recognition (ORB + DBoW) and the FPFH + RANSAC global alignment - every registration starts from the tracked
-poses (the identity between two segments of one world frame: the reference's method == "icp" branch, plus the Tukey fine stage of
-its "robust_icp" branch); which pairs are registered is `loop_closure.candidates` ('pose' or a callable).  TSDF fusion and the error
-plots are out as well.  What is registered are the segments' NEURAL points (on the device, thinned by the insertion radius), not
+  src/common.py  preprocess_point_cloud (voxel, FPFH)       fpfh_features -> lk_voxel_downsample, lk_normals, lk_fpfh
+  src/common.py  execute_global_registration (RANSAC)      global_registration -> lk_feature_match, lk_ransac_hypotheses, lk_ransac_score
+
+Out of scope: place recognition (ORB + DBoW); which pairs are registered is `loop_closure.candidates` ('pose' or a callable).  The
+methods 'icp' and 'robust_icp' start from the tracked poses (the identity between two segments of one world frame: the reference's
+method == "icp" branch, plus the Tukey fine stage of its "robust_icp" branch); 'fpfh_robust_icp' puts the reference's global start in
+front of them - voxel downsample, FPFH, mutual feature matches, 3-point RANSAC, all on the device - and survives a loop that has really
+drifted.  TSDF fusion and the error plots are out as well.  What is registered are the segments' NEURAL points (on the device, thinned by the insertion radius), not
 the raw back-projected sensor points the reference keeps per fragment.  Of the reference's edge filters only the
 `old_trans_mag_filter` branch (its default) is built.  Feature rows are not touched (rotation-agnostic in the reference too).
 """
@@ -24,7 +28,10 @@ from . import _ffi, core
 from ._ffi import ptr
 
 COARSE_DIST, FINE_DIST, TUKEY_K, NORMAL_RADIUS = 0.3, 0.03, 0.01, 0.1      # src/common.py:594-595, 607, 647
-METHODS = ('identity', 'icp', 'robust_icp')
+METHODS = ('identity', 'icp', 'robust_icp', 'fpfh_robust_icp')
+# the global start (src/common.py preprocess_point_cloud / execute_global_registration): voxel, normals over 2 voxels, features over 5,
+# checkers at 0.9 and 1.5 voxels, confidence and trial cap of the reference
+VOXEL, EDGE_RATIO, GLOBAL_CONF, GLOBAL_ITER, RANSAC_BATCH = 0.04, 0.9, 0.99999, 10_000_000, 65536
 
 
 # ------------------------------------------------------------------------------------------------ SE(3), fp64, vectors (omega, v)
@@ -93,6 +100,13 @@ class SegmentCloud:
         self.camera = np.asarray(torch.as_tensor(camera).detach().cpu().numpy(), dtype=np.float64).reshape(-1)[:3]
         self.cell = float(cell)
         self._knn = self._normals = None
+        self._features = {}
+
+    def features(self, voxel=VOXEL):
+        """fpfh_features of this cloud, computed once per voxel size."""
+        if voxel not in self._features:
+            self._features[voxel] = fpfh_features(self.eng, self.pos, self.camera, voxel)
+        return self._features[voxel]
 
     def __len__(self):
         return int(self.pos.shape[0])
@@ -199,10 +213,187 @@ def information_matrix(eng, src, tgt, T, max_dist=FINE_DIST):
     return A, cnt, sd2
 
 
-def register_pair(seg_s, seg_t, method='robust_icp', adjacent=False, eng=None):
+# ------------------------------------------------------------------------------------------------ global start: FPFH + RANSAC
+def _sync(eng):
+    if eng.device.type == 'cuda':
+        torch.cuda.current_stream(eng.device).synchronize()
+
+
+def _compact(eng, mask):
+    """Indices of the non-zero entries of a uint8 mask, ascending (lk_compact_large): (index [n] int32 with the first `count` filled,
+    count [1] int32, both on the device)."""
+    n = int(mask.shape[0])
+    index, count = eng.empty(max(n, 1), dtype=torch.int32), eng.zeros(1, dtype=torch.int32)
+    scratch = eng.empty(max((n + 255) // 256, 1), dtype=torch.int32)
+    eng.lib.check(eng.lib.dll.lk_compact_large(ptr(mask), n, ptr(index), ptr(count), ptr(scratch), eng.stream), 'lk_compact_large')
+    return index, count
+
+
+def voxel_downsample(eng, pos, voxel=VOXEL):
+    """One centroid per occupied voxel of edge `voxel`, in ascending voxel-key order (lk_voxel_keys -> sort -> lk_voxel_downsample); the
+    voxel grid starts half a voxel below the cloud's minimum, as Open3D's does."""
+    pos = pos.contiguous()
+    N = int(pos.shape[0])
+    if N == 0:
+        return eng.zeros(0, 3)
+    dll = eng.lib.dll
+    origin = pos.min(0).values.cpu().numpy().astype(np.float32) - np.float32(0.5) * np.float32(voxel)
+    keys = eng.empty(N, dtype=torch.int64)
+    eng.lib.check(dll.lk_voxel_keys(ptr(pos), N, (C.c_float * 3)(*origin.tolist()), C.c_float(voxel), ptr(keys), eng.stream), 'lk_voxel_keys')
+    skeys, order = torch.sort(keys, stable=True)
+    head = eng.empty(N, dtype=torch.uint8)
+    eng.lib.check(dll.lk_voxel_heads(ptr(skeys), N, ptr(head), eng.stream), 'lk_voxel_heads')
+    starts, count = _compact(eng, head)
+    n_vox = int(count.cpu()[0])
+    out = eng.empty(n_vox, 3)
+    order = order.contiguous()
+    eng.lib.check(dll.lk_voxel_downsample(ptr(pos), N, ptr(order), ptr(starts), n_vox, ptr(out), eng.stream), 'lk_voxel_downsample')
+    _sync(eng)
+    return out
+
+
+def _canonical_index(eng, pos, cell):
+    knn = core.KnnIndex(eng, capacity=max(int(pos.shape[0]), 1), cell_size=cell)
+    knn.build(pos)
+    eng.lib.check(eng.lib.dll.lk_knn_canonicalize(knn.h, eng.stream), 'lk_knn_canonicalize')
+    return knn
+
+
+def fpfh(eng, pos, normals, valid, radius):
+    """(spfh [N,33], fpfh [N,33]) of a cloud with normals (lk_fpfh) over an index of `radius` cells in canonical order."""
+    pos = pos.contiguous()
+    N = int(pos.shape[0])
+    spfh, out = eng.zeros(N, _ffi.FPFH_DIM), eng.zeros(N, _ffi.FPFH_DIM)
+    knn = _canonical_index(eng, pos, radius)
+    try:
+        eng.lib.check(eng.lib.dll.lk_fpfh(knn.h, ptr(pos), ptr(normals), ptr(valid), N, C.c_float(radius), ptr(spfh), ptr(out), eng.stream),
+                      'lk_fpfh')
+        _sync(eng)
+    finally:
+        knn.close()
+    return spfh, out
+
+
+def fpfh_features(eng, pos, camera, voxel=VOXEL):
+    """preprocess_point_cloud: downsample to `voxel`, normals over 2 voxels (towards `camera`), FPFH over 5 voxels.
+    Returns dict(pos, normals, valid, spfh, fpfh) on the device."""
+    down = voxel_downsample(eng, pos, voxel)
+    knn = _canonical_index(eng, down, 2.0 * voxel)
+    try:
+        normals, valid = estimate_normals(eng, down, 2.0 * voxel, camera, knn=knn)
+        _sync(eng)
+    finally:
+        knn.close()
+    spfh, feat = fpfh(eng, down, normals, valid, 5.0 * voxel)
+    return {'pos': down, 'normals': normals, 'valid': valid, 'spfh': spfh, 'fpfh': feat}
+
+
+def feature_match(eng, A, valid_a, B, valid_b):
+    """(index [Na] int32, d2 [Na]) of the nearest row of B for every row of A under (d2, index); -1 where there is none (lk_feature_match)."""
+    Na, Nb = int(A.shape[0]), int(B.shape[0])
+    idx, d2 = eng.empty(Na, dtype=torch.int32), eng.empty(Na)
+    eng.lib.check(eng.lib.dll.lk_feature_match(ptr(A), ptr(valid_a), Na, ptr(B), ptr(valid_b), Nb, ptr(idx), ptr(d2), eng.stream),
+                  'lk_feature_match')
+    return idx, d2
+
+
+def mutual_matches(eng, fs, ft):
+    """Correspondences [M,2] int32 (source row, target row) in source order: the pairs that choose each other, or - fewer than three of
+    those - every source row's own choice."""
+    m_st, _ = feature_match(eng, fs['fpfh'], fs['valid'], ft['fpfh'], ft['valid'])
+    m_ts, _ = feature_match(eng, ft['fpfh'], ft['valid'], fs['fpfh'], fs['valid'])
+    Ns = int(m_st.shape[0])
+    if Ns == 0 or int(m_ts.shape[0]) == 0:
+        return torch.zeros(0, 2, dtype=torch.int32, device=eng.device)
+    has = m_st >= 0
+    back = m_ts[m_st.clamp(min=0).long()]
+    mutual = (has & (back == torch.arange(Ns, dtype=torch.int32, device=eng.device))).to(torch.uint8)
+    rows, count = _compact(eng, mutual)
+    n = int(count.cpu()[0])
+    if n < 3:
+        rows, count = _compact(eng, has.to(torch.uint8))
+        n = int(count.cpu()[0])
+    rows = rows[:n]
+    return torch.stack([rows, m_st[rows.long()]], 1).contiguous()
+
+
+def ransac_batch(eng, cs, ct, seed, trial0, n_trials, dist_thr, edge_ratio=EDGE_RATIO, want_triples=False):
+    """One batch of trials (lk_ransac_hypotheses -> lk_compact_large -> lk_ransac_score): dict(triples or None, ok [n] uint8, T [n,12],
+    survivors [n] int32, n_survivors [1] int32, count [n] int32, sum_d2 [n]) on the device; the last two hold one entry per survivor."""
+    dll, M = eng.lib.dll, int(cs.shape[0])
+    triples = eng.empty(n_trials, 3, dtype=torch.int32) if want_triples else None
+    ok, T = eng.empty(n_trials, dtype=torch.uint8), eng.empty(n_trials, 12)
+    eng.lib.check(dll.lk_ransac_hypotheses(ptr(cs), ptr(ct), M, int(seed), int(trial0), n_trials, C.c_float(edge_ratio), C.c_float(dist_thr),
+                                           ptr(triples), ptr(ok), ptr(T), eng.stream), 'lk_ransac_hypotheses')
+    surv, n_surv = _compact(eng, ok)
+    count, sum_d2 = eng.zeros(n_trials, dtype=torch.int32), eng.zeros(n_trials)
+    eng.lib.check(dll.lk_ransac_score(ptr(cs), ptr(ct), M, ptr(T), ptr(surv), ptr(n_surv), n_trials, C.c_float(dist_thr), ptr(count),
+                                      ptr(sum_d2), eng.stream), 'lk_ransac_score')
+    return {'triples': triples, 'ok': ok, 'T': T, 'survivors': surv, 'n_survivors': n_surv, 'count': count, 'sum_d2': sum_d2}
+
+
+def rigid_fit(a, b):
+    """Least-squares rotation and translation (no scale, det = +1) taking the points a [n,3] onto b [n,3], fp64: 4 x 4."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    ma, mb = a.mean(0), b.mean(0)
+    U, _, Vt = np.linalg.svd((b - mb).T @ (a - ma))
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0])
+    T = np.eye(4)
+    T[:3, :3] = U @ D @ Vt
+    T[:3, 3] = mb - T[:3, :3] @ ma
+    return T
+
+
+def ransac(eng, src_pos, tgt_pos, corr, dist_thr, conf=GLOBAL_CONF, max_iter=GLOBAL_ITER, seed=0, batch=RANSAC_BATCH):
+    """RANSAC over the correspondences corr [M,2] in batches of `batch` trials, the best hypothesis (inlier count over the correspondence
+    set, then sum d2, then trial) read back after each; stops after k = log(1 - conf) / log(1 - ratio^3) trials, ratio = best count / M
+    (Open3D's rule), or max_iter.  The best hypothesis is then re-fitted over all its inlier correspondences here in fp64.
+    Returns dict(T, T_best, inliers, n_corr, trials, survivors, global_ok)."""
+    M = int(corr.shape[0])
+    out = {'T': np.eye(4), 'T_best': np.eye(4), 'inliers': 0, 'n_corr': M, 'trials': 0, 'survivors': 0, 'global_ok': False}
+    if M < 3:
+        return out
+    dll = eng.lib.dll
+    cs, ct = eng.empty(M, 3), eng.empty(M, 3)
+    eng.lib.check(dll.lk_ransac_gather(ptr(src_pos), ptr(tgt_pos), ptr(corr), M, ptr(cs), ptr(ct), eng.stream), 'lk_ransac_gather')
+    best = eng.zeros(_ffi.RANSAC_BEST, dtype=torch.int32)
+    best[0] = -1
+    trials, k_stop, b = 0, float(max_iter), None
+    while trials < min(k_stop, max_iter):
+        n = int(min(batch, max_iter - trials))
+        r = ransac_batch(eng, cs, ct, seed, trials, n, dist_thr)
+        eng.lib.check(dll.lk_ransac_best(ptr(r['count']), ptr(r['sum_d2']), ptr(r['survivors']), ptr(r['n_survivors']), ptr(r['T']),
+                                         trials, ptr(best), eng.stream), 'lk_ransac_best')
+        trials += n
+        b = best.cpu().numpy()               # the one synchronisation of a batch
+        if b[0] > 0:
+            ratio3 = min(float(b[0]) / M, 1.0) ** 3
+            k_stop = 0.0 if ratio3 >= 1.0 else np.log(1.0 - conf) / np.log(1.0 - ratio3)
+    out.update(trials=trials, survivors=int(b[16]))
+    if b[0] < 0:
+        return out
+    T = np.eye(4)
+    T[:3, :4] = b[4:16].view(np.float32).astype(np.float64).reshape(3, 4)
+    s64, t64 = cs.cpu().numpy().astype(np.float64), ct.cpu().numpy().astype(np.float64)
+    inl = (((s64 @ T[:3, :3].T + T[:3, 3]) - t64) ** 2).sum(1) <= float(dist_thr) ** 2
+    out.update(T_best=T, T=rigid_fit(s64[inl], t64[inl]) if inl.sum() >= 3 else T, inliers=int(b[0]), global_ok=True)
+    return out
+
+
+def global_registration(eng, seg_s, seg_t, voxel=VOXEL, conf=GLOBAL_CONF, max_iter=GLOBAL_ITER, seed=0):
+    """execute_global_registration for two SegmentClouds: FPFH features of both (cached on the clouds), mutual nearest feature matches,
+    RANSAC with the edge-length checker at 0.9 and the distance checker at 1.5 voxels.  Returns ransac()'s dict: T moves seg_s onto seg_t;
+    fewer than 3 correspondences or no surviving hypothesis: the identity and global_ok = False."""
+    fs, ft = seg_s.features(voxel), seg_t.features(voxel)
+    corr = mutual_matches(eng, fs, ft)
+    return ransac(eng, fs['pos'], ft['pos'], corr, 1.5 * voxel, conf, max_iter, seed)
+
+
+def register_pair(seg_s, seg_t, method='robust_icp', adjacent=False, eng=None, global_cfg=None):
     """src/common.py pairwise_registration + register_point_cloud_pair for two SegmentClouds, starting from the identity.
     'identity': the odometry edge of adjacent segments; 'icp': coarse 0.3 m then fine 0.03 m; 'robust_icp': coarse 0.3 m plain, then
-    fine 0.03 m with the Tukey loss k = 0.01.  A non-adjacent pair whose transform stays the identity or whose overlap
+    fine 0.03 m with the Tukey loss k = 0.01; 'fpfh_robust_icp': the same two stages started from global_registration's transform
+    (global_cfg: its conf / max_iter / seed; without a global result exactly 'robust_icp').  A non-adjacent pair whose transform stays the identity or whose overlap
     information[5,5] / n_points is below 0.3 fails: identity transform, identity information."""
     if method not in METHODS:
         raise NotImplementedError(f'loop_closure.method {method!r}: one of {METHODS}')
@@ -211,8 +402,13 @@ def register_pair(seg_s, seg_t, method='robust_icp', adjacent=False, eng=None):
     if method == 'identity':
         T = np.eye(4)
     else:
-        coarse = icp(eng, seg_s, seg_t, np.eye(4), COARSE_DIST)
-        fine = icp(eng, seg_s, seg_t, coarse['T'], FINE_DIST, TUKEY_K if method == 'robust_icp' else 0.0)
+        init = np.eye(4)
+        if method == 'fpfh_robust_icp':
+            g = global_registration(eng, seg_s, seg_t, **(global_cfg or {}))
+            init = g['T'] if g['global_ok'] else init
+            out.update(T_global=init, global_inliers=g['inliers'], global_trials=g['trials'], global_ok=g['global_ok'])
+        coarse = icp(eng, seg_s, seg_t, init, COARSE_DIST)
+        fine = icp(eng, seg_s, seg_t, coarse['T'], FINE_DIST, TUKEY_K if method != 'icp' else 0.0)
         T = fine['T']
         out.update(fitness=fine['fitness'], inlier_rmse=fine['inlier_rmse'], iterations=coarse['iterations'] + fine['iterations'],
                    T_coarse=coarse['T'])
@@ -316,7 +512,8 @@ def optimize_pose_graph(n_nodes, edges, prune=0.25, lc_pref=5.0, max_dist=FINE_D
 
 
 # ------------------------------------------------------------------------------------------------ the closer
-DEFAULTS = {'enabled': False, 'method': 'robust_icp', 'candidates': 'pose', 'max_center_dist': 1.5, 'min_axis_cos': 0.5}
+DEFAULTS = {'enabled': False, 'method': 'robust_icp', 'candidates': 'pose', 'max_center_dist': 1.5, 'min_axis_cos': 0.5,
+            'global_conf': GLOBAL_CONF, 'global_iter': GLOBAL_ITER, 'global_seed': 0}      # the last three: 'fpfh_robust_icp' only
 
 
 def settings(cfg):
@@ -340,6 +537,7 @@ class LoopCloser:
         tr = cfg.get('tracking', {})
         self.cfg, self.npc, self.slam, self.eng = lc, npc, slam, npc.eng
         self.method, self.candidates = lc['method'], lc['candidates']
+        self.global_cfg = {'conf': float(lc['global_conf']), 'max_iter': int(lc['global_iter']), 'seed': int(lc['global_seed'])}
         self.min_dist = tr.get('min_dist', 1)
         self.prune_pgo, self.lc_pref = tr.get('prune_pgo', 0.25), tr.get('lc_pref', 5.0)
         self.fitness_thresh, self.std_threshold = tr.get('fitness_thresh', 0.1), tr.get('std_threshold', 0.04)
@@ -409,7 +607,7 @@ class LoopCloser:
         try:
             regs = []
             for s, t in pairs:
-                r = register_pair(cloud(s), cloud(t), self.method, adjacent=False, eng=self.eng)
+                r = register_pair(cloud(s), cloud(t), self.method, adjacent=False, eng=self.eng, global_cfg=self.global_cfg)
                 r.update(s=s, t=t)
                 regs.append(r)
             self.last_registrations = regs

@@ -1,0 +1,202 @@
+"""The kernels of the global start of loop closure (csrc/lk_greg.hip) against the fp64 referee tests/greg_referee.py, on the host emulator
+and, under -m gpu, on the chip.  Input: the furnished-room segment pair of the referee.  Every stage is compared on the device's own inputs
+to that stage (its downsampled points, its normals, its SPFH table, its correspondences), so a stage answers for itself alone.  Bounds:
+  downsample    the referee's voxel set; centroids within 1e-5 m
+  SPFH          per point, the summed |difference| over the 33 bins <= 2 x increment x (pair features of the point the referee finds
+                within 1e-4 of a bin edge) + 1e-3; no point left out
+  FPFH          the referee's pass 2 on the device's SPFH and the fp32 contract distances: within 2e-4 (of the blocks' 100)
+  match         the chosen row's fp64 distance within a relative 1e-5 of the fp64 minimum for every query; the index equal wherever the
+                minimum is more than a relative 1e-5 from the runner-up
+  hypotheses    65 536 trials at seeds 0 and 1: equal triples; the same survivors except trials the referee marks within a relative 1e-5 of a
+                checker threshold, those at most 1 % of the survivors; transforms within 1e-4; inlier counts (the referee scoring the
+                device's transform: the scoring kernel answers for its own input) equal up to the correspondences within 1e-5 of 0.06 m
+  degenerate    an empty cloud, two correspondences, all normals invalid: the identity, global_ok False, no error
+  repeatable    two runs from fresh clouds, one seed: equal bits in every output; seeds 0 and 1 both inside the end-to-end bound
+"""
+import numpy as np
+import pytest
+import torch
+
+import greg_referee as G
+import lc_referee as R
+import util
+from loopy_slam_amd import loop_closure as LC
+
+DIST = 1.5 * G.VOXEL
+_DEV = {}
+
+
+def segments(eng, pair):
+    return (LC.SegmentCloud(eng, torch.from_numpy(pair['src']), pair['cam_s']), LC.SegmentCloud(eng, torch.from_numpy(pair['tgt']), pair['cam_t']))
+
+
+def device_chain(backend):
+    """The device's features, correspondences and gathered correspondence points of the pair, once per backend."""
+    if backend not in _DEV:
+        eng = util.make_engine(backend)
+        pair = G.segment_pair()
+        ss, st = segments(eng, pair)
+        fs, ft = ss.features(), st.features()
+        corr = LC.mutual_matches(eng, fs, ft)
+        M = int(corr.shape[0])
+        cs, ct = eng.empty(M, 3), eng.empty(M, 3)
+        eng.lib.check(eng.lib.dll.lk_ransac_gather(LC.ptr(fs['pos']), LC.ptr(ft['pos']), LC.ptr(corr), M, LC.ptr(cs), LC.ptr(ct), eng.stream),
+                      'lk_ransac_gather')
+        _DEV[backend] = {'eng': eng, 'pair': pair, 'fs': fs, 'ft': ft, 'corr': corr, 'cs': cs, 'ct': ct}
+    return _DEV[backend]
+
+
+def host(d):
+    return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_downsample(backend):
+    d = device_chain(backend)
+    for name, key in (('src', 'fs'), ('tgt', 'ft')):
+        ref, _ = G.voxel_downsample(d['pair'][name])
+        got = d[key]['pos'].cpu().numpy()
+        # ascending key order on both sides: with equal sets the rows pair up, with different ones they would be voxels apart
+        assert got.shape == ref.shape, name
+        err = float(np.abs(got - ref).max())
+        print(f'downsample {name}: {len(d["pair"][name])} -> {len(ref)} voxels, worst centroid error {err:.2e} m')
+        assert err <= 1e-5
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_spfh(backend):
+    d = device_chain(backend)
+    for key in ('fs', 'ft'):
+        f = host(d[key])
+        ref, cnt, near = G.spfh(f['pos'], f['normals'], f['valid'], 5.0 * G.VOXEL)
+        incr = np.where(cnt > 0, 100.0 / np.maximum(cnt, 1), 0.0)
+        diff = np.abs(f['spfh'].astype(np.float64) - ref).sum(1)
+        excess = diff - (2.0 * incr * near + 1e-3)
+        print(f'SPFH {key}: {len(ref)} points, {cnt.mean():.0f} neighbours on average, {int((near > 0).sum())} points with a feature at a bin '
+              f'edge, worst excess over the bound {excess.max():.3e} (largest difference {diff.max():.3e})')
+        assert (excess <= 0.0).all()
+        assert not f['spfh'][f['valid'] == 0].any()
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_fpfh(backend):
+    d = device_chain(backend)
+    for key in ('fs', 'ft'):
+        f = host(d[key])
+        ref = G.fpfh_pass2(f['spfh'], f['pos'], f['valid'], 5.0 * G.VOXEL)
+        err = float(np.abs(f['fpfh'].astype(np.float64) - ref).max())
+        print(f'FPFH {key}: worst difference {err:.2e} of 100')
+        assert err <= 2e-4
+        assert not f['fpfh'][f['valid'] == 0].any()
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_match(backend):
+    d = device_chain(backend)
+    eng, fs, ft = d['eng'], host(d['fs']), host(d['ft'])
+    for (a, va, b, vb, A, B) in ((d['fs']['fpfh'], d['fs']['valid'], d['ft']['fpfh'], d['ft']['valid'], fs, ft),
+                                 (d['ft']['fpfh'], d['ft']['valid'], d['fs']['fpfh'], d['fs']['valid'], ft, fs)):
+        idx, _ = LC.feature_match(eng, a, va, b, vb)
+        got = idx.cpu().numpy().astype(np.int64)
+        ref, d1, d2 = G.match(A['fpfh'], A['valid'], B['fpfh'], B['valid'])
+        assert np.array_equal(got < 0, ref < 0)
+        q = got >= 0
+        assert (B['valid'][got[q]] != 0).all()
+        chosen = ((A['fpfh'][q].astype(np.float64) - B['fpfh'][got[q]].astype(np.float64)) ** 2).sum(1)
+        assert (chosen <= d1[q] * (1.0 + 1e-5)).all()
+        clear = (d2[q] - d1[q]) > 1e-5 * d2[q]
+        print(f'match: {int(q.sum())} queries, {int((~clear).sum())} with the runner-up within 1e-5, {int((got[q] != ref[q]).sum())} other index')
+        assert np.array_equal(got[q][clear], ref[q][clear])
+    # the mutual pairs, in source order
+    m_st, _ = LC.feature_match(eng, d['fs']['fpfh'], d['fs']['valid'], d['ft']['fpfh'], d['ft']['valid'])
+    m_ts, _ = LC.feature_match(eng, d['ft']['fpfh'], d['ft']['valid'], d['fs']['fpfh'], d['fs']['valid'])
+    assert np.array_equal(d['corr'].cpu().numpy().astype(np.int64), G.mutual(m_st.cpu().numpy(), m_ts.cpu().numpy()))
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_hypotheses(backend):
+    d = device_chain(backend)
+    eng, corr = d['eng'], d['corr'].cpu().numpy()
+    cs, ct = d['cs'].cpu().numpy(), d['ct'].cpu().numpy()
+    assert np.array_equal(cs, d['fs']['pos'].cpu().numpy()[corr[:, 0]]) and np.array_equal(ct, d['ft']['pos'].cpu().numpy()[corr[:, 1]])
+    n = LC.RANSAC_BATCH
+    for seed in (0, 1):
+        r = host({k: v for k, v in LC.ransac_batch(eng, d['cs'], d['ct'], seed, 0, n, DIST, want_triples=True).items()})
+        ref = G.hypotheses(cs, ct, seed, 0, n, DIST)
+        assert np.array_equal(r['triples'].astype(np.int64), ref['triples'])
+        ok = r['ok'] != 0
+        n_surv = int(r['n_survivors'][0])
+        assert np.array_equal(r['survivors'][:n_surv], np.nonzero(ok)[0])              # compacted in trial order
+        differ = ok != ref['ok']
+        marked = ref['near'] & (ok | ref['ok'])
+        print(f'hypotheses seed {seed}: {int(ref["ok"].sum())} survivors of {n} trials, {int(marked.sum())} at a checker threshold, '
+              f'{int(differ.sum())} decided the other way')
+        assert not (differ & ~ref['near']).any()
+        assert marked.sum() <= 0.01 * ref['ok'].sum()
+        both = np.nonzero(ok & ref['ok'])[0]
+        T = np.tile(np.eye(4), (n, 1, 1))
+        T[:, :3, :4] = r['T'].astype(np.float64).reshape(n, 3, 4)
+        err = float(np.abs(T[both] - ref['T'][both]).max())
+        worst_count = 0
+        pos = {int(t): h for h, t in enumerate(r['survivors'][:n_surv])}
+        for t in both:
+            c, _, slack = G.score(cs, ct, T[t], DIST)
+            worst_count = max(worst_count, abs(int(r['count'][pos[int(t)]]) - c) - slack)
+        print(f'   transforms within {err:.2e} of the referee\'s, inlier counts beyond the threshold slack: {worst_count}')
+        assert err <= 1e-4
+        assert worst_count <= 0
+        assert not r['T'][~ok].any()
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_degenerate_inputs(backend):
+    eng = util.make_engine(backend)
+    pair = G.segment_pair()
+    _, st = segments(eng, pair)
+    empty = LC.SegmentCloud(eng, torch.zeros(0, 3), (0.0, 0.0, 0.0))
+    lattice = torch.stack(torch.meshgrid(*[torch.arange(4.0)] * 3, indexing='ij'), -1).reshape(-1, 3)      # 1 m apart: no normal is valid
+    sparse = LC.SegmentCloud(eng, lattice, (0.0, 0.0, 0.0))
+    assert not sparse.features()['valid'].any() and not sparse.features()['fpfh'].any()
+    for a, b in ((empty, st), (st, empty), (empty, empty), (sparse, st), (st, sparse)):
+        g = LC.global_registration(eng, a, b)
+        assert np.array_equal(g['T'], np.eye(4)) and g['global_ok'] is False and g['n_corr'] == 0 and g['trials'] == 0
+    fs, ft = st.features(), st.features()
+    two = torch.tensor([[0, 0], [5, 5]], dtype=torch.int32, device=eng.device)
+    g = LC.ransac(eng, fs['pos'], ft['pos'], two, DIST)
+    assert np.array_equal(g['T'], np.eye(4)) and g['global_ok'] is False and g['n_corr'] == 2
+    # register_pair without a global result goes on exactly as 'robust_icp' does
+    r1 = LC.register_pair(sparse, sparse, 'fpfh_robust_icp', adjacent=True, eng=eng)
+    r2 = LC.register_pair(sparse, sparse, 'robust_icp', adjacent=True, eng=eng)
+    assert r1['global_ok'] is False and np.array_equal(r1['T'], r2['T']) and np.array_equal(r1['information'], r2['information'])
+
+
+@pytest.mark.parametrize('backend', util.backends())
+def test_repeatability(backend):
+    eng = util.make_engine(backend)
+    pair = G.segment_pair()
+    runs = []
+    for _ in range(2):
+        ss, st = segments(eng, pair)                             # fresh clouds: every index is built again
+        fs, ft = ss.features(), st.features()
+        corr = LC.mutual_matches(eng, fs, ft)
+        M = int(corr.shape[0])
+        cs, ct = eng.empty(M, 3), eng.empty(M, 3)
+        eng.lib.check(eng.lib.dll.lk_ransac_gather(LC.ptr(fs['pos']), LC.ptr(ft['pos']), LC.ptr(corr), M, LC.ptr(cs), LC.ptr(ct), eng.stream),
+                      'lk_ransac_gather')
+        b = LC.ransac_batch(eng, cs, ct, 3, LC.RANSAC_BATCH, LC.RANSAC_BATCH, DIST, want_triples=True)
+        ns = int(b['n_survivors'].cpu()[0])
+        g = LC.global_registration(eng, ss, st, seed=3)
+        out = [fs[k] for k in ('pos', 'normals', 'valid', 'spfh', 'fpfh')] + [ft[k] for k in ('pos', 'normals', 'valid', 'spfh', 'fpfh')]
+        out += [corr, cs, ct, b['triples'], b['ok'], b['T'], b['survivors'][:ns], b['count'][:ns], b['sum_d2'][:ns]]
+        runs.append([x.cpu().numpy().tobytes() for x in out] + [g['T'].tobytes(), g['T_best'].tobytes(), repr((g['inliers'], g['trials'], g['survivors']))])
+        ss.close(); st.close()
+    assert [a == b for a, b in zip(*runs)] == [True] * len(runs[0])
+    # two seeds, one basin: both inside the end-to-end bound (tests/test_global_registration.py)
+    ref = G.global_registration(pair, 0)
+    bound = 2.0 * float(np.abs(G.refine(pair, ref['ransac']['T']) - pair['T']).max())
+    ss, st = segments(eng, pair)
+    for seed in (0, 1):
+        r = LC.register_pair(ss, st, 'fpfh_robust_icp', eng=eng, global_cfg={'seed': seed})
+        err = float(np.abs(r['T'] - pair['T']).max())
+        print(f'seed {seed}: max |T - T_planted| = {err:.3e} (bound {bound:.3e}), {r["global_inliers"]} inliers after {r["global_trials"]} trials')
+        assert r['success'] and err <= bound

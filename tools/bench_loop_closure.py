@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Timing of the loop-closure back end on one MI355X (loopy_slam_amd/loop_closure.py, csrc/lk_reg.hip): normals, one coarse + fine
-registration, the information matrix, correction + index rebuild, at 30 k / 100 k / 1 M points per cloud.
+registration, the information matrix, correction + index rebuild, at 30 k / 100 k / 1 M points per cloud; with --global also the stages of
+the global start (csrc/lk_greg.hip) on a furnished-room pair under a large planted transform: voxel downsample, FPFH (normals included),
+the two-way feature match, RANSAC per 65 536 trials and register_pair 'fpfh_robust_icp' end to end.
 
 Every figure is the wall time of the whole call including its host synchronisations (an ICP iteration ends in one small copy), warm, the
 median of `--repeats` runs.  --referee also times the fp64 NumPy referee of tests/lc_referee.py on the host for the two smaller sizes: the
 reference's own stage needs Open3D and cannot run here, so this is the only context there is.
 
-    python tools/bench_loop_closure.py [--sizes 30000 100000 1000000] [--repeats 5] [--referee]
+    python tools/bench_loop_closure.py [--sizes 30000 100000 1000000] [--repeats 5] [--referee] [--global [--global-sizes 30000 100000]]
 """
 import argparse
 import os
@@ -39,6 +41,65 @@ def clouds(n):
     return np.ascontiguousarray(src.astype(np.float32)), np.ascontiguousarray(pos[a:a + n]), T
 
 
+GLOBAL_PLANTED = ((40.0, -25.0, 70.0), (1.2, -0.8, 0.4))       # degrees, metres: outside the 0.3-m ICP basin
+
+
+def furnished_pair(n):
+    """Two n-point clouds of the furnished room from loop poses 0, 3, 6, 9 and 5, 8, 11, 14 (three points per ray), the first moved by the
+    inverse of GLOBAL_PLANTED: (source, target, planted 4 x 4, source camera, target camera)."""
+    def cloud(poses, seed):
+        g = torch.Generator().manual_seed(seed)
+        per = (n // 3 + len(poses) - 1) // len(poses)
+        pts = []
+        for k in poses:
+            c2w = synthetic.loop_pose(k, 200, 'cpu')
+            i, j = torch.rand(per, generator=g) * (synthetic.TUM_INTR['W'] - 1), torch.rand(per, generator=g) * (synthetic.TUM_INTR['H'] - 1)
+            ro, rd = synthetic.pixel_rays(c2w, i, j)
+            d, _ = synthetic.furnished_hit(ro, rd)
+            pts += [ro + rd * (d * t)[:, None] for t in (0.98, 1.0, 1.02)]
+        pos = torch.cat(pts).float().numpy()
+        return pos[np.random.RandomState(seed).permutation(len(pos))[:n]], synthetic.loop_pose(poses[0], 200, 'cpu')[:3, 3].numpy().astype(np.float64)
+    src, cam_s = cloud((0, 3, 6, 9), 101)
+    tgt, cam_t = cloud((5, 8, 11, 14), 202)
+    T = LC.se3_exp(np.concatenate([np.deg2rad(GLOBAL_PLANTED[0]), np.zeros(3)]))
+    T[:3, 3] = GLOBAL_PLANTED[1]
+    src = ((src.astype(np.float64) - T[:3, 3]) @ T[:3, :3]).astype(np.float32)
+    return np.ascontiguousarray(src), np.ascontiguousarray(tgt), T, (cam_s - T[:3, 3]) @ T[:3, :3], cam_t
+
+
+def global_rows(eng, n, repeats, sync):
+    src, tgt, T, cam_s, cam_t = furnished_pair(n)
+    ps, pt = eng.f32(src), eng.f32(tgt)
+    fs, ft = LC.fpfh_features(eng, ps, cam_s), LC.fpfh_features(eng, pt, cam_t)
+    corr = LC.mutual_matches(eng, fs, ft)
+    M = int(corr.shape[0])
+    cs, ct = eng.empty(M, 3), eng.empty(M, 3)
+    eng.lib.check(eng.lib.dll.lk_ransac_gather(ptr(fs['pos']), ptr(ft['pos']), ptr(corr), M, ptr(cs), ptr(ct), eng.stream), 'lk_ransac_gather')
+    best = eng.zeros(20, dtype=torch.int32)
+
+    def batch():
+        r = LC.ransac_batch(eng, cs, ct, 0, 0, LC.RANSAC_BATCH, 1.5 * LC.VOXEL)
+        eng.lib.check(eng.lib.dll.lk_ransac_best(ptr(r['count']), ptr(r['sum_d2']), ptr(r['survivors']), ptr(r['n_survivors']), ptr(r['T']), 0,
+                                                 ptr(best), eng.stream), 'lk_ransac_best')
+        best.cpu()
+    res = {}
+
+    def end_to_end():
+        sc, tc = LC.SegmentCloud(eng, ps, cam_s), LC.SegmentCloud(eng, pt, cam_t)         # fresh clouds: nothing cached
+        res.update(LC.register_pair(sc, tc, 'fpfh_robust_icp'))
+        sc.close(); tc.close()
+    ns, nt = len(fs['pos']), len(ft['pos'])
+    return [
+        (n, f'voxel downsample 0.04 m (-> {ns:,} voxels)', timed(lambda: LC.voxel_downsample(eng, ps), repeats, sync), ''),
+        (n, 'fpfh_features: downsample + index + lk_normals 0.08 m + lk_fpfh 0.2 m', timed(lambda: LC.fpfh_features(eng, ps, cam_s), repeats, sync), ''),
+        (n, f'lk_fpfh alone incl. its index ({ns:,} points)', timed(lambda: LC.fpfh(eng, fs['pos'], fs['normals'], fs['valid'], 5 * LC.VOXEL), repeats, sync), ''),
+        (n, f'mutual_matches: lk_feature_match both ways ({ns:,} x {nt:,})', timed(lambda: LC.mutual_matches(eng, fs, ft), repeats, sync), f'{M} mutual pairs'),
+        (n, 'RANSAC, one batch of 65 536 trials (hypotheses + compact + score + best + read-back)', timed(batch, repeats, sync), ''),
+        (n, "register_pair 'fpfh_robust_icp' end to end, fresh clouds", timed(end_to_end, repeats, sync),
+         f"{res['global_trials']} trials, {res['global_inliers']} inliers, {res['iterations']} ICP iterations, max abs (T - planted) {np.abs(res['T'] - T).max():.1e}"),
+    ]
+
+
 def timed(fn, repeats, sync):
     fn()
     sync()
@@ -56,10 +117,16 @@ def main():
     ap.add_argument('--sizes', type=int, nargs='+', default=[30000, 100000, 1000000])
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--referee', action='store_true')
+    ap.add_argument('--global', dest='glob', action='store_true', help="time the stages of 'fpfh_robust_icp' instead")
+    ap.add_argument('--global-sizes', type=int, nargs='+', default=[30000, 100000])
     args = ap.parse_args()
     eng = core.Engine()
     sync = torch.cuda.synchronize
     rows = []
+    if args.glob:
+        args.sizes = []
+        for n in args.global_sizes:
+            rows += global_rows(eng, n, args.repeats, sync)
     for n in args.sizes:
         src, tgt, T = clouds(n)
         sc, tc = LC.SegmentCloud(eng, torch.from_numpy(src), (0, 0, 0)), LC.SegmentCloud(eng, torch.from_numpy(tgt), (0, 0, 0))
