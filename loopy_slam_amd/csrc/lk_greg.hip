@@ -9,12 +9,14 @@
 // All arithmetic is fp32.  Nothing here adds floating-point numbers through atomics: histograms are integer counts (LDS integer atomics,
 // order-free), every floating-point sum is walked in an order the inputs fix (the canonical cell order, the row order of a table, a fixed
 // butterfly), so equal inputs and an equal seed give equal bits.
+//
+// Shared with lk_reg.hip: the radius box and its row walk (lk_knn_dev.h: lk_grid_box, lk_box_rows), the 8-lane group, the rigid map and
+// the Jacobi rotation (lk_reg_dev.h).
 #include "lk_common.h"
 #include "lk_knn_dev.h"
+#include "lk_reg_dev.h"
 #include "lk_kernels.h"
 
-#define LK_GREG_T 8                                  // lanes per point (as lk_reg.hip)
-#define LK_GREG_GROUPS (256 / LK_GREG_T)
 #define LK_PI_F 3.14159265358979323846f
 
 // ------------------------------------------------------------------ voxel downsample
@@ -112,91 +114,67 @@ extern "C" int lk_knn_canonicalize(lk_knn_t h, void* stream_) {
 }
 
 // ------------------------------------------------------------------ FPFH
-// the box of grid rows around a query that holds every point within r (as k_normals)
-struct LkBox { int ix0, ix1, iy0, iy1, iz0, iz1; bool any; };
-__device__ __forceinline__ LkBox lk_box(const LkGrid* __restrict__ G, float qx, float qy, float qz, float r2) {
-    const float ox = G->ox, oy = G->oy, oz = G->oz, inv = G->inv_cell;
-    const int dx = G->dx, dy = G->dy, dz = G->dz;
-    const float r = sqrtf(r2) * 1.0001f + 1e-6f;
-    LkBox b;
-    b.any = G->n > 0;
-    b.any = b.any && !((qx + r - ox) * inv < 0.0f || (qx - r - ox) * inv >= (float)dx);
-    b.any = b.any && !((qy + r - oy) * inv < 0.0f || (qy - r - oy) * inv >= (float)dy);
-    b.any = b.any && !((qz + r - oz) * inv < 0.0f || (qz - r - oz) * inv >= (float)dz);
-    b.ix0 = lk_cell_coord(qx - r, ox, inv, dx); b.ix1 = lk_cell_coord(qx + r, ox, inv, dx);
-    b.iy0 = lk_cell_coord(qy - r, oy, inv, dy); b.iy1 = lk_cell_coord(qy + r, oy, inv, dy);
-    b.iz0 = lk_cell_coord(qz - r, oz, inv, dz); b.iz1 = lk_cell_coord(qz + r, oz, inv, dz);
-    return b;
-}
-
 __device__ __forceinline__ int lk_bin11(float x) { return (int)fminf(fmaxf(floorf(x), 0.0f), 10.0f); }
 
 // Pass 1.  One 8-lane group per point; the three 11-bin histograms are integer counts in LDS, scaled by 100 / count at the end.
 __global__ __launch_bounds__(256) void k_spfh(const LkGrid* __restrict__ G, const float4* __restrict__ sorted, const int32_t* __restrict__ cell_start,
                                               const float* __restrict__ pos, const float* __restrict__ nrm, const uint8_t* __restrict__ valid, int N,
                                               float r2, float* __restrict__ spfh) {
-    __shared__ unsigned hist[LK_GREG_GROUPS][LK_FPFH_DIM + 3];
-    const int group = (int)threadIdx.x / LK_GREG_T, sub = (int)threadIdx.x % LK_GREG_T;
-    const int qi_raw = blockIdx.x * LK_GREG_GROUPS + group;
+    __shared__ unsigned hist[LK_REG_GROUPS][LK_FPFH_DIM + 3];
+    const int group = (int)threadIdx.x / LK_REG_T, sub = (int)threadIdx.x % LK_REG_T;
+    const int qi_raw = blockIdx.x * LK_REG_GROUPS + group;
     const bool live = qi_raw < N;
     const int i = live ? qi_raw : N - 1;
-    for (int b = sub; b < LK_FPFH_DIM; b += LK_GREG_T) hist[group][b] = 0u;
+    for (int b = sub; b < LK_FPFH_DIM; b += LK_REG_T) hist[group][b] = 0u;
     __syncthreads();
     const float qx = pos[3 * (size_t)i], qy = pos[3 * (size_t)i + 1], qz = pos[3 * (size_t)i + 2];
     const float n1x = nrm[3 * (size_t)i], n1y = nrm[3 * (size_t)i + 1], n1z = nrm[3 * (size_t)i + 2];
     const bool own = valid[i] != 0;
     float cnt = 0.0f;
-    const LkBox bx = lk_box(G, qx, qy, qz, r2);
-    if (bx.any && own) {
+    if (own) {
+        lk_box_rows(G, cell_start, lk_grid_box(G, qx, qy, qz, lk_box_halfwidth(r2)), [&](int s, int e) {
 #pragma unroll 1
-        for (int iz = bx.iz0; iz <= bx.iz1; ++iz) {
-#pragma unroll 1
-            for (int iy = bx.iy0; iy <= bx.iy1; ++iy) {
-                const int row = (iz * G->dy + iy) * G->dx;
-                const int s = cell_start[row + bx.ix0], e = cell_start[row + bx.ix1 + 1];
-#pragma unroll 1
-                for (int t = s + sub; t < e; t += LK_GREG_T) {
-                    const float4 p = sorted[t];
-                    const int k = __float_as_int(p.w);
-                    const float d2 = lk_dist2(qx, qy, qz, p.x, p.y, p.z);
-                    if (d2 > r2 || k == i || !valid[k]) continue;
-                    cnt += 1.0f;
-                    const float n2x = nrm[3 * (size_t)k], n2y = nrm[3 * (size_t)k + 1], n2z = nrm[3 * (size_t)k + 2];
-                    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
-                    const float d = sqrtf(d2);
-                    if (d > 0.0f) {
-                        float ex = __fsub_rn(p.x, qx), ey = __fsub_rn(p.y, qy), ez = __fsub_rn(p.z, qz);
-                        const float a1 = (n1x * ex + n1y * ey + n1z * ez) / d, a2 = (n2x * ex + n2y * ey + n2z * ez) / d;
-                        // acos|a1| > acos|a2|.  The one decision taken in fp64 (exact differences, products of fp32 values): a neighbour along the
-                        // normal - the three points of one ray - has a1 = a2 up to rounding, and the swap turns f2 from -1 to +1
-                        const double gx = (double)p.x - (double)qx, gy = (double)p.y - (double)qy, gz = (double)p.z - (double)qz;
-                        const bool swap = fabs((double)n1x * gx + (double)n1y * gy + (double)n1z * gz) <
-                                          fabs((double)n2x * gx + (double)n2y * gy + (double)n2z * gz);
-                        const float ux = swap ? n2x : n1x, uy = swap ? n2y : n1y, uz = swap ? n2z : n1z;
-                        const float mx = swap ? n1x : n2x, my = swap ? n1y : n2y, mz = swap ? n1z : n2z;
-                        if (swap) { ex = -ex; ey = -ey; ez = -ez; }
-                        float vx = ey * uz - ez * uy, vy = ez * ux - ex * uz, vz = ex * uy - ey * ux;
-                        const float vn = sqrtf(vx * vx + vy * vy + vz * vz);
-                        if (vn > 0.0f) {
-                            vx /= vn; vy /= vn; vz /= vn;
-                            const float wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
-                            f2 = swap ? -a2 : a1;
-                            f1 = vx * mx + vy * my + vz * mz;
-                            f0 = atan2f(wx * mx + wy * my + wz * mz, ux * mx + uy * my + uz * mz);
-                        }
+            for (int t = s + sub; t < e; t += LK_REG_T) {
+                const float4 p = sorted[t];
+                const int k = __float_as_int(p.w);
+                const float d2 = lk_dist2(qx, qy, qz, p.x, p.y, p.z);
+                if (d2 > r2 || k == i || !valid[k]) continue;
+                cnt += 1.0f;
+                const float n2x = nrm[3 * (size_t)k], n2y = nrm[3 * (size_t)k + 1], n2z = nrm[3 * (size_t)k + 2];
+                float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+                const float d = sqrtf(d2);
+                if (d > 0.0f) {
+                    float ex = __fsub_rn(p.x, qx), ey = __fsub_rn(p.y, qy), ez = __fsub_rn(p.z, qz);
+                    const float a1 = (n1x * ex + n1y * ey + n1z * ez) / d, a2 = (n2x * ex + n2y * ey + n2z * ez) / d;
+                    // acos|a1| > acos|a2|.  The one decision taken in fp64 (exact differences, products of fp32 values): a neighbour along the
+                    // normal - the three points of one ray - has a1 = a2 up to rounding, and the swap turns f2 from -1 to +1
+                    const double gx = (double)p.x - (double)qx, gy = (double)p.y - (double)qy, gz = (double)p.z - (double)qz;
+                    const bool swap = fabs((double)n1x * gx + (double)n1y * gy + (double)n1z * gz) <
+                                      fabs((double)n2x * gx + (double)n2y * gy + (double)n2z * gz);
+                    const float ux = swap ? n2x : n1x, uy = swap ? n2y : n1y, uz = swap ? n2z : n1z;
+                    const float mx = swap ? n1x : n2x, my = swap ? n1y : n2y, mz = swap ? n1z : n2z;
+                    if (swap) { ex = -ex; ey = -ey; ez = -ez; }
+                    float vx = ey * uz - ez * uy, vy = ez * ux - ex * uz, vz = ex * uy - ey * ux;
+                    const float vn = sqrtf(vx * vx + vy * vy + vz * vz);
+                    if (vn > 0.0f) {
+                        vx /= vn; vy /= vn; vz /= vn;
+                        const float wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
+                        f2 = swap ? -a2 : a1;
+                        f1 = vx * mx + vy * my + vz * mz;
+                        f0 = atan2f(wx * mx + wy * my + wz * mz, ux * mx + uy * my + uz * mz);
                     }
-                    atomicAdd(&hist[group][lk_bin11(11.0f * (f0 + LK_PI_F) / (2.0f * LK_PI_F))], 1u);
-                    atomicAdd(&hist[group][11 + lk_bin11(11.0f * (f1 + 1.0f) * 0.5f)], 1u);
-                    atomicAdd(&hist[group][22 + lk_bin11(11.0f * (f2 + 1.0f) * 0.5f)], 1u);
                 }
+                atomicAdd(&hist[group][lk_bin11(11.0f * (f0 + LK_PI_F) / (2.0f * LK_PI_F))], 1u);
+                atomicAdd(&hist[group][11 + lk_bin11(11.0f * (f1 + 1.0f) * 0.5f)], 1u);
+                atomicAdd(&hist[group][22 + lk_bin11(11.0f * (f2 + 1.0f) * 0.5f)], 1u);
             }
-        }
+        });
     }
     cnt = lk_sum8(cnt);
     __syncthreads();
     if (!live) return;
     const float incr = cnt > 0.0f ? 100.0f / cnt : 0.0f;
-    for (int b = sub; b < LK_FPFH_DIM; b += LK_GREG_T) spfh[(size_t)i * LK_FPFH_DIM + b] = (float)hist[group][b] * incr;
+    for (int b = sub; b < LK_FPFH_DIM; b += LK_REG_T) spfh[(size_t)i * LK_FPFH_DIM + b] = (float)hist[group][b] * incr;
 }
 
 // Pass 2.  Lane `sub` of a point's group owns bins sub, sub + 8, ..; all eight lanes walk ALL neighbours in the canonical cell order, so a bin
@@ -204,10 +182,10 @@ __global__ __launch_bounds__(256) void k_spfh(const LkGrid* __restrict__ G, cons
 __global__ __launch_bounds__(256) void k_fpfh(const LkGrid* __restrict__ G, const float4* __restrict__ sorted, const int32_t* __restrict__ cell_start,
                                               const float* __restrict__ pos, const uint8_t* __restrict__ valid, int N, float r2,
                                               const float* __restrict__ spfh, float* __restrict__ fpfh) {
-    __shared__ float row[LK_GREG_GROUPS][LK_FPFH_DIM + 3];
-    constexpr int NB = (LK_FPFH_DIM + LK_GREG_T - 1) / LK_GREG_T;
-    const int group = (int)threadIdx.x / LK_GREG_T, sub = (int)threadIdx.x % LK_GREG_T;
-    const int qi_raw = blockIdx.x * LK_GREG_GROUPS + group;
+    __shared__ float row[LK_REG_GROUPS][LK_FPFH_DIM + 3];
+    constexpr int NB = (LK_FPFH_DIM + LK_REG_T - 1) / LK_REG_T;
+    const int group = (int)threadIdx.x / LK_REG_T, sub = (int)threadIdx.x % LK_REG_T;
+    const int qi_raw = blockIdx.x * LK_REG_GROUPS + group;
     const bool live = qi_raw < N;
     const int i = live ? qi_raw : N - 1;
     const float qx = pos[3 * (size_t)i], qy = pos[3 * (size_t)i + 1], qz = pos[3 * (size_t)i + 2];
@@ -215,32 +193,25 @@ __global__ __launch_bounds__(256) void k_fpfh(const LkGrid* __restrict__ G, cons
     float acc[NB];
 #pragma unroll
     for (int q = 0; q < NB; ++q) acc[q] = 0.0f;
-    const LkBox bx = lk_box(G, qx, qy, qz, r2);
-    if (bx.any && own) {
+    if (own) {
+        lk_box_rows(G, cell_start, lk_grid_box(G, qx, qy, qz, lk_box_halfwidth(r2)), [&](int s, int e) {
 #pragma unroll 1
-        for (int iz = bx.iz0; iz <= bx.iz1; ++iz) {
-#pragma unroll 1
-            for (int iy = bx.iy0; iy <= bx.iy1; ++iy) {
-                const int rw = (iz * G->dy + iy) * G->dx;
-                const int s = cell_start[rw + bx.ix0], e = cell_start[rw + bx.ix1 + 1];
-#pragma unroll 1
-                for (int t = s; t < e; ++t) {
-                    const float4 p = sorted[t];
-                    const int k = __float_as_int(p.w);
-                    const float d2 = lk_dist2(qx, qy, qz, p.x, p.y, p.z);
-                    if (d2 > r2 || k == i || !valid[k] || d2 == 0.0f) continue;
+            for (int t = s; t < e; ++t) {
+                const float4 p = sorted[t];
+                const int k = __float_as_int(p.w);
+                const float d2 = lk_dist2(qx, qy, qz, p.x, p.y, p.z);
+                if (d2 > r2 || k == i || !valid[k] || d2 == 0.0f) continue;
 #pragma unroll
-                    for (int q = 0; q < NB; ++q) {
-                        const int b = sub + LK_GREG_T * q;
-                        if (b < LK_FPFH_DIM) acc[q] += spfh[(size_t)k * LK_FPFH_DIM + b] / d2;
-                    }
+                for (int q = 0; q < NB; ++q) {
+                    const int b = sub + LK_REG_T * q;
+                    if (b < LK_FPFH_DIM) acc[q] += spfh[(size_t)k * LK_FPFH_DIM + b] / d2;
                 }
             }
-        }
+        });
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-        const int b = sub + LK_GREG_T * q;
+        const int b = sub + LK_REG_T * q;
         if (b < LK_FPFH_DIM) row[group][b] = acc[q];
     }
     __syncthreads();
@@ -254,7 +225,7 @@ __global__ __launch_bounds__(256) void k_fpfh(const LkGrid* __restrict__ G, cons
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-        const int b = sub + LK_GREG_T * q;
+        const int b = sub + LK_REG_T * q;
         if (b < LK_FPFH_DIM) {
             const float sc = b < 11 ? scale[0] : (b < 22 ? scale[1] : scale[2]);
             fpfh[(size_t)i * LK_FPFH_DIM + b] = own ? acc[q] * sc + spfh[(size_t)i * LK_FPFH_DIM + b] : 0.0f;
@@ -270,7 +241,7 @@ extern "C" int lk_fpfh(lk_knn_t knn, const float* pos, const float* normals, con
     if (N == 0) return LK_OK;
     LK_REQUIRE(pos && normals && valid && out_spfh && out_fpfh, "lk_fpfh: NULL buffer");
     hipStream_t st = (hipStream_t)stream_;
-    const dim3 grid(lk_cdiv(N, LK_GREG_GROUPS));
+    const dim3 grid(lk_cdiv(N, LK_REG_GROUPS));
     hipLaunchKernelGGL(k_spfh, grid, dim3(256), 0, st, (const LkGrid*)knn->grid, (const float4*)knn->sorted, (const int32_t*)knn->cell_start, pos,
                        normals, valid, (int)N, radius * radius, out_spfh);
     hipLaunchKernelGGL(k_fpfh, grid, dim3(256), 0, st, (const LkGrid*)knn->grid, (const float4*)knn->sorted, (const int32_t*)knn->cell_start, pos,
@@ -364,32 +335,6 @@ __global__ __launch_bounds__(256) void k_ransac_gather(const float* __restrict__
     for (int c = 0; c < 3; ++c) { cs[3 * (size_t)j + c] = src[3 * (size_t)a + c]; ct[3 * (size_t)j + c] = tgt[3 * (size_t)b + c]; }
 }
 
-template <int P, int Q>
-__device__ __forceinline__ void lk_jacobi4_rot(double (&a)[4][4], double (&v)[4][4]) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[P][P] -= t * apq;
-    a[Q][Q] += t * apq;
-    a[P][Q] = 0.0; a[Q][P] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r != P && r != Q) {
-            const double arp = a[r][P], arq = a[r][Q];
-            a[r][P] = c * arp - s * arq; a[P][r] = a[r][P];
-            a[r][Q] = s * arp + c * arq; a[Q][r] = a[r][Q];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vp = v[k][P], vq = v[k][Q];
-        v[k][P] = c * vp - s * vq;
-        v[k][Q] = s * vp + c * vq;
-    }
-}
-
 // One thread per trial: draw, check, fit (Horn 1987: the rotation is the unit eigenvector of the largest eigenvalue of a symmetric 4 x 4 matrix
 // of the centred cross-covariance; cyclic Jacobi), check again.  ok[t] = 1 and T[t] (row-major 3 x 4) for a survivor.
 __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ cs, const float* __restrict__ ct, int M, uint32_t seed_lo,
@@ -452,8 +397,8 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ cs
         double V[4][4] = {{1.0, 0.0, 0.0, 0.0}, {0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};
 #pragma unroll 1
         for (int sweep = 0; sweep < 12; ++sweep) {
-            lk_jacobi4_rot<0, 1>(Nm, V); lk_jacobi4_rot<0, 2>(Nm, V); lk_jacobi4_rot<0, 3>(Nm, V);
-            lk_jacobi4_rot<1, 2>(Nm, V); lk_jacobi4_rot<1, 3>(Nm, V); lk_jacobi4_rot<2, 3>(Nm, V);
+            lk_jacobi_rot<4, 0, 1>(Nm, V); lk_jacobi_rot<4, 0, 2>(Nm, V); lk_jacobi_rot<4, 0, 3>(Nm, V);
+            lk_jacobi_rot<4, 1, 2>(Nm, V); lk_jacobi_rot<4, 1, 3>(Nm, V); lk_jacobi_rot<4, 2, 3>(Nm, V);
         }
         double lmax = Nm[0][0];
         int col = 0;
@@ -476,9 +421,8 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const float* __restrict__ cs
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float px = __fmaf_rn(T[0], s[k][0], __fmaf_rn(T[1], s[k][1], __fmaf_rn(T[2], s[k][2], T[3])));
-            const float py = __fmaf_rn(T[4], s[k][0], __fmaf_rn(T[5], s[k][1], __fmaf_rn(T[6], s[k][2], T[7])));
-            const float pz = __fmaf_rn(T[8], s[k][0], __fmaf_rn(T[9], s[k][1], __fmaf_rn(T[10], s[k][2], T[11])));
+            float px, py, pz;
+            lk_rigid_apply(T, s[k][0], s[k][1], s[k][2], px, py, pz);
             ok = ok && !(sqrtf(lk_dist2(px, py, pz, q[k][0], q[k][1], q[k][2])) > dist_thr);
         }
     }
@@ -514,10 +458,8 @@ __global__ __launch_bounds__(256) void k_ransac_score(const float* __restrict__ 
         __syncthreads();
 #pragma unroll 1
         for (int j = lane; j < nj; j += 64) {
-            const float x = ls[3 * j], y = ls[3 * j + 1], z = ls[3 * j + 2];
-            const float px = __fmaf_rn(T[0], x, __fmaf_rn(T[1], y, __fmaf_rn(T[2], z, T[3])));
-            const float py = __fmaf_rn(T[4], x, __fmaf_rn(T[5], y, __fmaf_rn(T[6], z, T[7])));
-            const float pz = __fmaf_rn(T[8], x, __fmaf_rn(T[9], y, __fmaf_rn(T[10], z, T[11])));
+            float px, py, pz;
+            lk_rigid_apply(T, ls[3 * j], ls[3 * j + 1], ls[3 * j + 2], px, py, pz);
             const float d2 = lk_dist2(px, py, pz, lt[3 * j], lt[3 * j + 1], lt[3 * j + 2]);
             if (d2 <= thr2) { cnt += 1; sum += d2; }
         }

@@ -19,6 +19,43 @@ __device__ __forceinline__ int lk_cell_coord(float x, float o, float inv, int d)
     return (int)f;
 }
 
+// The radius box: the cells [ix0..ix1] x [iy0..iy1] x [iz0..iz1] that hold every point within the half-width r of q.  `any` is false when
+// the box lies wholly outside the grid (or the grid is empty); the y and z ranges are empty then, so a walk over the box does nothing.
+struct LkGridBox { int ix0, ix1, iy0, iy1, iz0, iz1; bool any; };
+
+// half-width for the contract d2 <= r2, slightly inflated: never misses a cell
+__device__ __forceinline__ float lk_box_halfwidth(float r2) { return sqrtf(r2) * 1.0001f + 1e-6f; }
+
+__device__ __forceinline__ LkGridBox lk_grid_box(const LkGrid* __restrict__ G, float qx, float qy, float qz, float r) {
+    const float ox = G->ox, oy = G->oy, oz = G->oz, inv = G->inv_cell;
+    const int dx = G->dx, dy = G->dy, dz = G->dz;
+    LkGridBox b = {0, -1, 0, -1, 0, -1, G->n > 0};
+    b.any = b.any && !((qx + r - ox) * inv < 0.0f || (qx - r - ox) * inv >= (float)dx);
+    b.any = b.any && !((qy + r - oy) * inv < 0.0f || (qy - r - oy) * inv >= (float)dy);
+    b.any = b.any && !((qz + r - oz) * inv < 0.0f || (qz - r - oz) * inv >= (float)dz);
+    if (b.any) {
+        b.ix0 = lk_cell_coord(qx - r, ox, inv, dx); b.ix1 = lk_cell_coord(qx + r, ox, inv, dx);
+        b.iy0 = lk_cell_coord(qy - r, oy, inv, dy); b.iy1 = lk_cell_coord(qy + r, oy, inv, dy);
+        b.iz0 = lk_cell_coord(qz - r, oz, inv, dz); b.iz1 = lk_cell_coord(qz + r, oz, inv, dz);
+    }
+    return b;
+}
+
+// fn(first, end) for the run of cell-sorted points of every (iz, iy) row of the box, z-major ascending; x is the fastest-varying cell
+// coordinate, so a row's cells [ix0..ix1] are ONE contiguous run.  The walk over the candidates of a run is the caller's.
+template <class F>
+__device__ __forceinline__ void lk_box_rows(const LkGrid* __restrict__ G, const int32_t* __restrict__ cell_start, const LkGridBox& b, F fn) {
+    const int dx = G->dx, dy = G->dy;
+#pragma unroll 1
+    for (int iz = b.iz0; iz <= b.iz1; ++iz) {
+#pragma unroll 1
+        for (int iy = b.iy0; iy <= b.iy1; ++iy) {
+            const int row = (iz * dy + iy) * dx;
+            fn(cell_start[row + b.ix0], cell_start[row + b.ix1 + 1]);
+        }
+    }
+}
+
 template <int V> struct LkInt { static constexpr int value = V; };
 // A candidate is ONE 64-bit key: (bits of d2) << 32 | index.  d2 >= +0, so the unsigned order of the float bits is the
 // float order and the key order is the strict total order (d2, index) in a single v_cmp_lt_u64.
@@ -75,6 +112,7 @@ __device__ __forceinline__ void lk_knn_merge_round(uint64_t (&k)[LK_K]) {
 // All T lanes of a group must call this convergently with the same query (qx,qy,qz,r2).
 // x is the fastest-varying cell coordinate, so the cells [ix0..ix1] of one (iy,iz) row are ONE
 // contiguous range of the cell-sorted point array.
+// (Not built on lk_grid_box / lk_box_rows: with them k_sample_interp<8, 1>, the benchmark's search kernel, goes from 128 to 129 VGPRs.)
 template <int T>
 __device__ __forceinline__ void lk_knn_scan_coop(const LkGrid* __restrict__ G, const float4* __restrict__ sorted,
                                                  const int32_t* __restrict__ cell_start,

@@ -11,39 +11,19 @@
 // Reductions are repeatable: a lane adds the terms of its queries in query order, the wave combines lanes with a fixed xor butterfly, the
 // workgroup adds its four waves in wave order and stores ONE row of LK_REG_OUT partials; a second one-workgroup launch adds the rows in
 // row order in fp64.  No floating-point atomics anywhere.
+//
+// Shared with lk_greg.hip: the radius box and its row walk (lk_knn_dev.h: lk_grid_box, lk_box_rows), the 8-lane group, the rigid map and
+// the Jacobi rotation (lk_reg_dev.h).
 #include "lk_common.h"
 #include "lk_knn_dev.h"
+#include "lk_reg_dev.h"
 #include "lk_kernels.h"
 
-#define LK_REG_T 8                                  // lanes per query (as the standalone search at size)
-#define LK_REG_GROUPS (256 / LK_REG_T)              // queries a workgroup works on at a time
 #define LK_REG_QPW 128                              // queries per workgroup: the grid follows the point count
 
 struct LkMat12 { float m[12]; };                    // row-major 3 x 4, passed by value
 
 // ------------------------------------------------------------------ normals
-template <int P, int Q>
-__device__ __forceinline__ void lk_jacobi_rot(float (&a)[3][3], float (&v)[3][3]) {
-    const float apq = a[P][Q];
-    if (apq == 0.0f) return;
-    constexpr int R = 3 - P - Q;
-    const float theta = (a[Q][Q] - a[P][P]) / (2.0f * apq);
-    const float t = (theta >= 0.0f ? 1.0f : -1.0f) / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
-    const float c = 1.0f / sqrtf(t * t + 1.0f), s = t * c;
-    a[P][P] -= t * apq;
-    a[Q][Q] += t * apq;
-    a[P][Q] = 0.0f; a[Q][P] = 0.0f;
-    const float arp = a[R][P], arq = a[R][Q];
-    a[R][P] = c * arp - s * arq; a[P][R] = a[R][P];
-    a[R][Q] = s * arp + c * arq; a[Q][R] = a[R][Q];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float vp = v[k][P], vq = v[k][Q];
-        v[k][P] = c * vp - s * vq;
-        v[k][Q] = s * vp + c * vq;
-    }
-}
-
 // unit eigenvector of the smallest eigenvalue of the symmetric matrix (xx xy xz; . yy yz; . . zz): cyclic Jacobi, fp32
 __device__ __forceinline__ void lk_smallest_eigvec(float xx, float xy, float xz, float yy, float yz, float zz, float& nx, float& ny, float& nz) {
     const float tr = xx + yy + zz;
@@ -52,9 +32,9 @@ __device__ __forceinline__ void lk_smallest_eigvec(float xx, float xy, float xz,
     float v[3][3] = {{1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
 #pragma unroll 1
     for (int sweep = 0; sweep < 8; ++sweep) {
-        lk_jacobi_rot<0, 1>(a, v);
-        lk_jacobi_rot<0, 2>(a, v);
-        lk_jacobi_rot<1, 2>(a, v);
+        lk_jacobi_rot<3, 0, 1>(a, v);
+        lk_jacobi_rot<3, 0, 2>(a, v);
+        lk_jacobi_rot<3, 1, 2>(a, v);
     }
     const float l0 = a[0][0], l1 = a[1][1], l2 = a[2][2];
     const bool p0 = l0 <= l1 && l0 <= l2, p1 = !p0 && l1 <= l2;
@@ -75,38 +55,20 @@ __global__ __launch_bounds__(256) void k_normals(const LkGrid* __restrict__ G, c
     const bool live = qi_raw < N;
     const int i = live ? qi_raw : N - 1;
     const float qx = pos[3 * (size_t)i], qy = pos[3 * (size_t)i + 1], qz = pos[3 * (size_t)i + 2];
-    const float ox = G->ox, oy = G->oy, oz = G->oz, inv = G->inv_cell;
-    const int dx = G->dx, dy = G->dy, dz = G->dz;
-    const float r = sqrtf(r2) * 1.0001f + 1e-6f;          // box slightly inflated: never misses a cell
-    bool any = G->n > 0;
-    any = any && !((qx + r - ox) * inv < 0.0f || (qx - r - ox) * inv >= (float)dx);
-    any = any && !((qy + r - oy) * inv < 0.0f || (qy - r - oy) * inv >= (float)dy);
-    any = any && !((qz + r - oz) * inv < 0.0f || (qz - r - oz) * inv >= (float)dz);
     float cnt = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sxx = 0.0f, sxy = 0.0f, sxz = 0.0f, syy = 0.0f, syz = 0.0f, szz = 0.0f;
-    if (any) {
-        const int ix0 = lk_cell_coord(qx - r, ox, inv, dx), ix1 = lk_cell_coord(qx + r, ox, inv, dx);
-        const int iy0 = lk_cell_coord(qy - r, oy, inv, dy), iy1 = lk_cell_coord(qy + r, oy, inv, dy);
-        const int iz0 = lk_cell_coord(qz - r, oz, inv, dz), iz1 = lk_cell_coord(qz + r, oz, inv, dz);
+    lk_box_rows(G, cell_start, lk_grid_box(G, qx, qy, qz, lk_box_halfwidth(r2)), [&](int s, int e) {
 #pragma unroll 1
-        for (int iz = iz0; iz <= iz1; ++iz) {
-#pragma unroll 1
-            for (int iy = iy0; iy <= iy1; ++iy) {
-                const int row = (iz * dy + iy) * dx;
-                const int s = cell_start[row + ix0], e = cell_start[row + ix1 + 1];
-#pragma unroll 1
-                for (int t = s + sub; t < e; t += LK_REG_T) {
-                    const float4 p = sorted[t];
-                    if (lk_dist2(qx, qy, qz, p.x, p.y, p.z) <= r2) {
-                        const float ax = p.x - qx, ay = p.y - qy, az = p.z - qz;
-                        cnt += 1.0f;
-                        sx += ax; sy += ay; sz += az;
-                        sxx += ax * ax; sxy += ax * ay; sxz += ax * az;
-                        syy += ay * ay; syz += ay * az; szz += az * az;
-                    }
-                }
+        for (int t = s + sub; t < e; t += LK_REG_T) {
+            const float4 p = sorted[t];
+            if (lk_dist2(qx, qy, qz, p.x, p.y, p.z) <= r2) {
+                const float ax = p.x - qx, ay = p.y - qy, az = p.z - qz;
+                cnt += 1.0f;
+                sx += ax; sy += ay; sz += az;
+                sxx += ax * ax; sxy += ax * ay; sxz += ax * az;
+                syy += ay * ay; syz += ay * az; szz += az * az;
             }
         }
-    }
+    });
     cnt = lk_sum8(cnt);
     sx = lk_sum8(sx); sy = lk_sum8(sy); sz = lk_sum8(sz);
     sxx = lk_sum8(sxx); sxy = lk_sum8(sxy); sxz = lk_sum8(sxz);
@@ -154,15 +116,11 @@ __device__ __forceinline__ uint64_t lk_group_min8(uint64_t k) {
 __device__ __forceinline__ uint64_t lk_nearest_coop(const LkGrid* __restrict__ G, const float4* __restrict__ sorted,
                                                     const int32_t* __restrict__ cell_start, float qx, float qy, float qz, float r2, int sub) {
     uint64_t best = LK_KEY_EMPTY;
-    const float ox = G->ox, oy = G->oy, oz = G->oz, inv = G->inv_cell;
-    const int dx = G->dx, dy = G->dy, dz = G->dz;
-    const float rfull = sqrtf(r2) * 1.0001f + 1e-6f;      // box slightly inflated: never misses a cell
+    const float rfull = lk_box_halfwidth(r2);
     const float cellf = G->cell;
     const bool big = rfull > cellf * 1.05f;
     const float r = big ? cellf * 0.9999f - 1e-6f : rfull;
-    auto walk = [&](int row, int xa, int xb) {
-        if (xa > xb) return;
-        const int s = cell_start[row + xa], e = cell_start[row + xb + 1];
+    auto walk = [&](int s, int e) {
 #pragma unroll 1
         for (int t = s + sub; t < e; t += LK_REG_T) {
             const float4 p = sorted[t];
@@ -171,36 +129,26 @@ __device__ __forceinline__ uint64_t lk_nearest_coop(const LkGrid* __restrict__ G
             if (d2 <= r2 && key < best) best = key;
         }
     };
-    auto outside = [&](float h) {
-        return G->n <= 0 || (qx + h - ox) * inv < 0.0f || (qx - h - ox) * inv >= (float)dx || (qy + h - oy) * inv < 0.0f ||
-               (qy - h - oy) * inv >= (float)dy || (qz + h - oz) * inv < 0.0f || (qz - h - oz) * inv >= (float)dz;
-    };
-    const bool any = !outside(r);
-    int ix0 = 0, ix1 = -1, iy0 = 0, iy1 = -1, iz0 = 0, iz1 = -1;
-    if (any) {
-        ix0 = lk_cell_coord(qx - r, ox, inv, dx); ix1 = lk_cell_coord(qx + r, ox, inv, dx);
-        iy0 = lk_cell_coord(qy - r, oy, inv, dy); iy1 = lk_cell_coord(qy + r, oy, inv, dy);
-        iz0 = lk_cell_coord(qz - r, oz, inv, dz); iz1 = lk_cell_coord(qz + r, oz, inv, dz);
-#pragma unroll 1
-        for (int iz = iz0; iz <= iz1; ++iz)
-#pragma unroll 1
-            for (int iy = iy0; iy <= iy1; ++iy) walk((iz * dy + iy) * dx, ix0, ix1);
-    }
+    const LkGridBox b1 = lk_grid_box(G, qx, qy, qz, r);
+    lk_box_rows(G, cell_start, b1, walk);
     best = lk_group_min8(best);
     // (every lane of the group holds the same key here, so the decision is group-uniform)
     const bool done = !big || (best != LK_KEY_EMPTY && __uint_as_float((uint32_t)(best >> 32)) <= r * r * (1.0f - 1e-6f));
-    if (!done && !outside(rfull)) {
-        const int fx0 = lk_cell_coord(qx - rfull, ox, inv, dx), fx1 = lk_cell_coord(qx + rfull, ox, inv, dx);
-        const int fy0 = lk_cell_coord(qy - rfull, oy, inv, dy), fy1 = lk_cell_coord(qy + rfull, oy, inv, dy);
-        const int fz0 = lk_cell_coord(qz - rfull, oz, inv, dz), fz1 = lk_cell_coord(qz + rfull, oz, inv, dz);
+    if (!done) {
+        // the full box minus what phase 1 has seen: [ix0, ix1] of the rows of its box (an empty phase-1 box has no rows)
+        const LkGridBox bf = lk_grid_box(G, qx, qy, qz, rfull);
+        const int dx = G->dx, dy = G->dy;
+        auto part = [&](int row, int xa, int xb) {
+            if (xa <= xb) walk(cell_start[row + xa], cell_start[row + xb + 1]);
+        };
 #pragma unroll 1
-        for (int iz = fz0; iz <= fz1; ++iz) {
+        for (int iz = bf.iz0; iz <= bf.iz1; ++iz) {
 #pragma unroll 1
-            for (int iy = fy0; iy <= fy1; ++iy) {
+            for (int iy = bf.iy0; iy <= bf.iy1; ++iy) {
                 const int row = (iz * dy + iy) * dx;
-                const bool seen = any && iz >= iz0 && iz <= iz1 && iy >= iy0 && iy <= iy1;     // phase 1 scanned [ix0, ix1] of this row
-                if (!seen) walk(row, fx0, fx1);
-                else { walk(row, fx0, ix0 - 1); walk(row, ix1 + 1, fx1); }
+                const bool seen = iz >= b1.iz0 && iz <= b1.iz1 && iy >= b1.iy0 && iy <= b1.iy1;
+                if (!seen) part(row, bf.ix0, bf.ix1);
+                else { part(row, bf.ix0, b1.ix0 - 1); part(row, b1.ix1 + 1, bf.ix1); }
             }
         }
     }
@@ -224,9 +172,8 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const LkGrid* __restrict
         const bool live = qi_raw < P;
         const int i = live ? qi_raw : P - 1;             // dead groups shadow the last query (the search's collectives stay convergent)
         const float px = src[3 * (size_t)i], py = src[3 * (size_t)i + 1], pz = src[3 * (size_t)i + 2];
-        const float sx = __fmaf_rn(M.m[0], px, __fmaf_rn(M.m[1], py, __fmaf_rn(M.m[2], pz, M.m[3])));
-        const float sy = __fmaf_rn(M.m[4], px, __fmaf_rn(M.m[5], py, __fmaf_rn(M.m[6], pz, M.m[7])));
-        const float sz = __fmaf_rn(M.m[8], px, __fmaf_rn(M.m[9], py, __fmaf_rn(M.m[10], pz, M.m[11])));
+        float sx, sy, sz;
+        lk_rigid_apply(M.m, px, py, pz, sx, sy, sz);
         const uint64_t key = lk_nearest_coop(G, sorted, cell_start, sx, sy, sz, r2, sub);
         const int j = (int)(uint32_t)key;                // -1 when the key is the empty one
         const float d2 = __uint_as_float((uint32_t)(key >> 32));
@@ -351,9 +298,7 @@ __global__ __launch_bounds__(256) void k_apply_correction(float* __restrict__ po
                        m[7] == 0.0f && m[8] == 0.0f && m[9] == 0.0f && m[10] == 1.0f && m[11] == 0.0f;
     if (ident) return;                                    // bit-identical, signed zeros included
     const float x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
-    pos[3 * i] = __fmaf_rn(m[0], x, __fmaf_rn(m[1], y, __fmaf_rn(m[2], z, m[3])));
-    pos[3 * i + 1] = __fmaf_rn(m[4], x, __fmaf_rn(m[5], y, __fmaf_rn(m[6], z, m[7])));
-    pos[3 * i + 2] = __fmaf_rn(m[8], x, __fmaf_rn(m[9], y, __fmaf_rn(m[10], z, m[11])));
+    lk_rigid_apply(m, x, y, z, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
 }
 
 extern "C" int lk_apply_correction(float* pos, int64_t N, const int32_t* seg_id, const float* mats, int32_t n_seg, void* stream_) {

@@ -87,6 +87,11 @@ def _inv(T):
 
 
 # ------------------------------------------------------------------------------------------------ device layer
+def _sync(eng):
+    if eng.device.type == 'cuda':
+        torch.cuda.current_stream(eng.device).synchronize()
+
+
 class SegmentCloud:
     """The points of one segment on the device with what a registration needs of them: one grid index and the normals.
 
@@ -142,8 +147,7 @@ def estimate_normals(eng, pos, radius=NORMAL_RADIUS, camera=(0.0, 0.0, 0.0), knn
     cam = (C.c_float * 3)(*[float(c) for c in np.asarray(camera, dtype=np.float64).reshape(-1)[:3]])
     eng.lib.check(eng.lib.dll.lk_normals(knn.h, ptr(pos), N, C.c_float(radius), cam, ptr(normals), ptr(valid), eng.stream), 'lk_normals')
     if own:
-        if eng.device.type == 'cuda':
-            torch.cuda.current_stream(eng.device).synchronize()
+        _sync(eng)
         knn.close()
     return normals, valid
 
@@ -214,11 +218,6 @@ def information_matrix(eng, src, tgt, T, max_dist=FINE_DIST):
 
 
 # ------------------------------------------------------------------------------------------------ global start: FPFH + RANSAC
-def _sync(eng):
-    if eng.device.type == 'cuda':
-        torch.cuda.current_stream(eng.device).synchronize()
-
-
 def _compact(eng, mask):
     """Indices of the non-zero entries of a uint8 mask, ascending (lk_compact_large): (index [n] int32 with the first `count` filled,
     count [1] int32, both on the device)."""
@@ -332,6 +331,27 @@ def ransac_batch(eng, cs, ct, seed, trial0, n_trials, dist_thr, edge_ratio=EDGE_
     return {'triples': triples, 'ok': ok, 'T': T, 'survivors': surv, 'n_survivors': n_surv, 'count': count, 'sum_d2': sum_d2}
 
 
+def ransac_gather(eng, src_pos, tgt_pos, corr):
+    """(cs [M,3], ct [M,3]): the source and target points of the correspondences corr [M,2] (lk_ransac_gather)."""
+    M = int(corr.shape[0])
+    cs, ct = eng.empty(M, 3), eng.empty(M, 3)
+    eng.lib.check(eng.lib.dll.lk_ransac_gather(ptr(src_pos), ptr(tgt_pos), ptr(corr), M, ptr(cs), ptr(ct), eng.stream), 'lk_ransac_gather')
+    return cs, ct
+
+
+def ransac_best_init(eng):
+    """The device record lk_ransac_best folds into, before the first batch: best[0] = -1 (none yet), the rest 0."""
+    best = eng.zeros(_ffi.RANSAC_BEST, dtype=torch.int32)
+    best[0] = -1
+    return best
+
+
+def ransac_fold(eng, r, trial0, best):
+    """Fold the ransac_batch result r, whose first trial is trial0, into the record `best` (lk_ransac_best)."""
+    eng.lib.check(eng.lib.dll.lk_ransac_best(ptr(r['count']), ptr(r['sum_d2']), ptr(r['survivors']), ptr(r['n_survivors']), ptr(r['T']),
+                                             int(trial0), ptr(best), eng.stream), 'lk_ransac_best')
+
+
 def rigid_fit(a, b):
     """Least-squares rotation and translation (no scale, det = +1) taking the points a [n,3] onto b [n,3], fp64: 4 x 4."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
@@ -353,17 +373,13 @@ def ransac(eng, src_pos, tgt_pos, corr, dist_thr, conf=GLOBAL_CONF, max_iter=GLO
     out = {'T': np.eye(4), 'T_best': np.eye(4), 'inliers': 0, 'n_corr': M, 'trials': 0, 'survivors': 0, 'global_ok': False}
     if M < 3:
         return out
-    dll = eng.lib.dll
-    cs, ct = eng.empty(M, 3), eng.empty(M, 3)
-    eng.lib.check(dll.lk_ransac_gather(ptr(src_pos), ptr(tgt_pos), ptr(corr), M, ptr(cs), ptr(ct), eng.stream), 'lk_ransac_gather')
-    best = eng.zeros(_ffi.RANSAC_BEST, dtype=torch.int32)
-    best[0] = -1
+    cs, ct = ransac_gather(eng, src_pos, tgt_pos, corr)
+    best = ransac_best_init(eng)
     trials, k_stop, b = 0, float(max_iter), None
     while trials < min(k_stop, max_iter):
         n = int(min(batch, max_iter - trials))
         r = ransac_batch(eng, cs, ct, seed, trials, n, dist_thr)
-        eng.lib.check(dll.lk_ransac_best(ptr(r['count']), ptr(r['sum_d2']), ptr(r['survivors']), ptr(r['n_survivors']), ptr(r['T']),
-                                         trials, ptr(best), eng.stream), 'lk_ransac_best')
+        ransac_fold(eng, r, trials, best)
         trials += n
         b = best.cpu().numpy()               # the one synchronisation of a batch
         if b[0] > 0:
@@ -618,8 +634,7 @@ class LoopCloser:
                 if (i, i + 1) not in self.odometry_info:
                     self.odometry_info[(i, i + 1)] = register_pair(cloud(i), cloud(i + 1), 'identity', adjacent=True, eng=self.eng)['information']
         finally:
-            if self.eng.device.type == 'cuda':
-                torch.cuda.current_stream(self.eng.device).synchronize()
+            _sync(self.eng)
             for c in clouds.values():
                 c.close()
         edges = [(i, i + 1, np.eye(4), self.odometry_info[(i, i + 1)], False) for i in range(n - 1)] + self.loop_edges + new_loops

@@ -10,6 +10,7 @@ no network.
 """
 import math
 
+import numpy as np
 import torch
 
 ROOM = (6.0, 4.0, 3.0)
@@ -178,6 +179,34 @@ def build_cloud(n_points, device='cpu', seed=1219, intr=TUM_INTR, n_views=24, c_
     geo = (0.1 * torch.randn(pos.shape[0], c_dim, generator=g)).float()
     col = (0.1 * torch.randn(pos.shape[0], c_dim, generator=g)).float()
     return pos.to(device), geo.to(device), col.to(device)
+
+
+def overlapping_pair(n_each, seed=5):
+    """Two overlapping n_each-point clouds of the plain room (numpy [n,3] fp32): rows [0, n) and [2n/3, 5n/3) of a fixed permutation of
+    build_cloud(2n, seed) - one third shared points, the rest different samples of the same surfaces."""
+    pos = build_cloud(2 * n_each, seed=seed)[0].numpy()
+    pos = pos[np.random.RandomState(0).permutation(len(pos))]
+    a = (2 * n_each) // 3
+    return np.ascontiguousarray(pos[:n_each]), np.ascontiguousarray(pos[a:a + n_each])
+
+
+def furnished_cloud(poses, n_points, seed):
+    """n_points of the FURNISHED room seen from the loop poses `poses` (numpy [n,3] fp32) and the first pose's camera centre (fp64):
+    n_points / 3 rays spread over the poses, three points per ray as build_cloud makes them, in a fixed permutation."""
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    per_view = (n_points // 3 + len(poses) - 1) // len(poses)
+    pts = []
+    for k in poses:
+        c2w = loop_pose(k, 200, 'cpu')
+        i = torch.rand(per_view, generator=g) * (TUM_INTR['W'] - 1)
+        j = torch.rand(per_view, generator=g) * (TUM_INTR['H'] - 1)
+        ro, rd = pixel_rays(c2w, i, j)
+        d, _ = furnished_hit(ro, rd)
+        for t in (0.98, 1.0, 1.02):
+            pts.append(ro + rd * (d * t)[:, None])
+    pos = torch.cat(pts, 0).float().numpy()
+    pos = pos[np.random.RandomState(seed).permutation(len(pos))[:n_points]]
+    return np.ascontiguousarray(pos), loop_pose(poses[0], 200, 'cpu')[:3, 3].numpy().astype(np.float64)
 
 
 ROOM_PITCH = 8.0          # metres between the rooms of a multi-room map (x axis): the walls of neighbouring rooms are 2 m apart

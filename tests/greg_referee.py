@@ -28,22 +28,8 @@ _CACHE = {}
 
 def furnished_cloud(poses, n_points, seed):
     """[n_points,3] fp32 and the first pose's camera centre: n_points / 3 rays spread over the poses, three points per ray."""
-    import torch
     from loopy_slam_amd import synthetic
-    g = torch.Generator(device='cpu').manual_seed(seed)
-    per_view = (n_points // 3 + len(poses) - 1) // len(poses)
-    pts = []
-    for k in poses:
-        c2w = synthetic.loop_pose(k, 200, 'cpu')
-        i = torch.rand(per_view, generator=g) * (synthetic.TUM_INTR['W'] - 1)
-        j = torch.rand(per_view, generator=g) * (synthetic.TUM_INTR['H'] - 1)
-        ro, rd = synthetic.pixel_rays(c2w, i, j)
-        d, _ = synthetic.furnished_hit(ro, rd)
-        for t in (0.98, 1.0, 1.02):
-            pts.append(ro + rd * (d * t)[:, None])
-    pos = torch.cat(pts, 0).float().numpy()
-    pos = pos[np.random.RandomState(seed).permutation(len(pos))[:n_points]]
-    return np.ascontiguousarray(pos), synthetic.loop_pose(poses[0], 200, 'cpu')[:3, 3].numpy().astype(np.float64)
+    return synthetic.furnished_cloud(poses, n_points, seed)
 
 
 def segment_pair(n=30000, planted=PLANTED):

@@ -235,10 +235,7 @@ def clouds(n_each=30000, seed=5):
     """(source [n,3], target [n,3]) fp32: rows [0, n) and [2n/3, 5n/3) of a fixed permutation of synthetic.build_cloud(2n, seed):
     one third shared points, the rest different samples of the same surfaces."""
     from loopy_slam_amd import synthetic
-    pos = synthetic.build_cloud(2 * n_each, seed=seed)[0].numpy()
-    pos = pos[np.random.RandomState(0).permutation(len(pos))]
-    a = (2 * n_each) // 3
-    return np.ascontiguousarray(pos[:n_each]), np.ascontiguousarray(pos[a:a + n_each])
+    return synthetic.overlapping_pair(n_each, seed)
 
 
 def move(pts, T):

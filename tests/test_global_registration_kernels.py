@@ -38,10 +38,7 @@ def device_chain(backend):
         ss, st = segments(eng, pair)
         fs, ft = ss.features(), st.features()
         corr = LC.mutual_matches(eng, fs, ft)
-        M = int(corr.shape[0])
-        cs, ct = eng.empty(M, 3), eng.empty(M, 3)
-        eng.lib.check(eng.lib.dll.lk_ransac_gather(LC.ptr(fs['pos']), LC.ptr(ft['pos']), LC.ptr(corr), M, LC.ptr(cs), LC.ptr(ct), eng.stream),
-                      'lk_ransac_gather')
+        cs, ct = LC.ransac_gather(eng, fs['pos'], ft['pos'], corr)
         _DEV[backend] = {'eng': eng, 'pair': pair, 'fs': fs, 'ft': ft, 'corr': corr, 'cs': cs, 'ct': ct}
     return _DEV[backend]
 
@@ -179,10 +176,7 @@ def test_repeatability(backend):
         ss, st = segments(eng, pair)                             # fresh clouds: every index is built again
         fs, ft = ss.features(), st.features()
         corr = LC.mutual_matches(eng, fs, ft)
-        M = int(corr.shape[0])
-        cs, ct = eng.empty(M, 3), eng.empty(M, 3)
-        eng.lib.check(eng.lib.dll.lk_ransac_gather(LC.ptr(fs['pos']), LC.ptr(ft['pos']), LC.ptr(corr), M, LC.ptr(cs), LC.ptr(ct), eng.stream),
-                      'lk_ransac_gather')
+        cs, ct = LC.ransac_gather(eng, fs['pos'], ft['pos'], corr)
         b = LC.ransac_batch(eng, cs, ct, 3, LC.RANSAC_BATCH, LC.RANSAC_BATCH, DIST, want_triples=True)
         ns = int(b['n_survivors'].cpu()[0])
         g = LC.global_registration(eng, ss, st, seed=3)

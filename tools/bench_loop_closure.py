@@ -33,12 +33,10 @@ def planted():
 
 
 def clouds(n):
-    pos = synthetic.build_cloud(2 * n, seed=5)[0].numpy()
-    pos = pos[np.random.RandomState(0).permutation(len(pos))]
-    a = (2 * n) // 3
+    src, tgt = synthetic.overlapping_pair(n, seed=5)
     T = planted()
-    src = (pos[:n].astype(np.float64) - T[:3, 3]) @ T[:3, :3]          # moved by the inverse of the planted transform
-    return np.ascontiguousarray(src.astype(np.float32)), np.ascontiguousarray(pos[a:a + n]), T
+    src = (src.astype(np.float64) - T[:3, 3]) @ T[:3, :3]              # moved by the inverse of the planted transform
+    return np.ascontiguousarray(src.astype(np.float32)), tgt, T
 
 
 GLOBAL_PLANTED = ((40.0, -25.0, 70.0), (1.2, -0.8, 0.4))       # degrees, metres: outside the 0.3-m ICP basin
@@ -47,24 +45,12 @@ GLOBAL_PLANTED = ((40.0, -25.0, 70.0), (1.2, -0.8, 0.4))       # degrees, metres
 def furnished_pair(n):
     """Two n-point clouds of the furnished room from loop poses 0, 3, 6, 9 and 5, 8, 11, 14 (three points per ray), the first moved by the
     inverse of GLOBAL_PLANTED: (source, target, planted 4 x 4, source camera, target camera)."""
-    def cloud(poses, seed):
-        g = torch.Generator().manual_seed(seed)
-        per = (n // 3 + len(poses) - 1) // len(poses)
-        pts = []
-        for k in poses:
-            c2w = synthetic.loop_pose(k, 200, 'cpu')
-            i, j = torch.rand(per, generator=g) * (synthetic.TUM_INTR['W'] - 1), torch.rand(per, generator=g) * (synthetic.TUM_INTR['H'] - 1)
-            ro, rd = synthetic.pixel_rays(c2w, i, j)
-            d, _ = synthetic.furnished_hit(ro, rd)
-            pts += [ro + rd * (d * t)[:, None] for t in (0.98, 1.0, 1.02)]
-        pos = torch.cat(pts).float().numpy()
-        return pos[np.random.RandomState(seed).permutation(len(pos))[:n]], synthetic.loop_pose(poses[0], 200, 'cpu')[:3, 3].numpy().astype(np.float64)
-    src, cam_s = cloud((0, 3, 6, 9), 101)
-    tgt, cam_t = cloud((5, 8, 11, 14), 202)
+    src, cam_s = synthetic.furnished_cloud((0, 3, 6, 9), n, 101)
+    tgt, cam_t = synthetic.furnished_cloud((5, 8, 11, 14), n, 202)
     T = LC.se3_exp(np.concatenate([np.deg2rad(GLOBAL_PLANTED[0]), np.zeros(3)]))
     T[:3, 3] = GLOBAL_PLANTED[1]
     src = ((src.astype(np.float64) - T[:3, 3]) @ T[:3, :3]).astype(np.float32)
-    return np.ascontiguousarray(src), np.ascontiguousarray(tgt), T, (cam_s - T[:3, 3]) @ T[:3, :3], cam_t
+    return np.ascontiguousarray(src), tgt, T, (cam_s - T[:3, 3]) @ T[:3, :3], cam_t
 
 
 def global_rows(eng, n, repeats, sync):
@@ -73,14 +59,11 @@ def global_rows(eng, n, repeats, sync):
     fs, ft = LC.fpfh_features(eng, ps, cam_s), LC.fpfh_features(eng, pt, cam_t)
     corr = LC.mutual_matches(eng, fs, ft)
     M = int(corr.shape[0])
-    cs, ct = eng.empty(M, 3), eng.empty(M, 3)
-    eng.lib.check(eng.lib.dll.lk_ransac_gather(ptr(fs['pos']), ptr(ft['pos']), ptr(corr), M, ptr(cs), ptr(ct), eng.stream), 'lk_ransac_gather')
-    best = eng.zeros(20, dtype=torch.int32)
+    cs, ct = LC.ransac_gather(eng, fs['pos'], ft['pos'], corr)
+    best = LC.ransac_best_init(eng)
 
     def batch():
-        r = LC.ransac_batch(eng, cs, ct, 0, 0, LC.RANSAC_BATCH, 1.5 * LC.VOXEL)
-        eng.lib.check(eng.lib.dll.lk_ransac_best(ptr(r['count']), ptr(r['sum_d2']), ptr(r['survivors']), ptr(r['n_survivors']), ptr(r['T']), 0,
-                                                 ptr(best), eng.stream), 'lk_ransac_best')
+        LC.ransac_fold(eng, LC.ransac_batch(eng, cs, ct, 0, 0, LC.RANSAC_BATCH, 1.5 * LC.VOXEL), 0, best)
         best.cpu()
     res = {}
 
