@@ -626,6 +626,52 @@ int lk_ransac_score(const float* cs, const float* ct, int32_t M, const float* T_
 int lk_ransac_best(const int32_t* count, const float* sum_d2, const int32_t* survivors, const int32_t* n_survivors, const float* T_all,
                    uint64_t trial0, int32_t* best, void* stream);
 
+/* ---------------------------------------------------------------- TSDF fusion and meshing
+ * What the reference does with Open3D's ScalableTSDFVolume at the end of a run (src/tools/get_mesh_tsdf_fusion.py).  fp32 throughout, no
+ * atomics: every voxel, cube and vertex has one owning thread, so equal inputs give equal bits.
+ *
+ * Volume.  A block is 16^3 voxels of edge `voxel`; block (bx, by, bz) = floor(p / (16 voxel)) per axis has the key
+ * ((bx + 2^20) << 42) | ((by + 2^20) << 21) | (bz + 2^20) (the bit order of lk_voxel_keys).  Blocks live in slots in allocation order:
+ * slot_keys[n_slots] holds their keys, planes[n_slots][5][4096] their tsdf, weight, r, g, b (r, g, b in 0 .. 255), a plane in [z][y][x] order;
+ * a new slot is all zeros.  The centre of voxel i of block b along an axis is ((float)(16 b + i) + 0.5f) * voxel.
+ *
+ * Camera.  host_c2w16: HOST pointer, row-major 4 x 4 of the project's camera (x right, y up, looking down -z).  Both calls negate its columns 1
+ * and 2 (the reference's flip into Open3D's axes) once on the host; lk_tsdf_integrate inverts the result in fp64 and rounds once.  Points are
+ * moved by three fused multiply-adds per coordinate, as in lk_icp_accumulate.
+ *
+ * lk_tsdf_touch: every stride-th pixel (rows 0, stride, ..; columns likewise; sample s = (row / stride) * ceil(W / stride) + column / stride) with
+ * 0 < depth < depth_trunc is back-projected, p = c2w ((px - cx) d / fx, (py - cy) d / fy, d), and out_keys[s][0..8) receives the keys of the blocks
+ * that the box p +- sdf_trunc overlaps (floor((p - sdf_trunc) / (16 voxel)) .. floor((p + sdf_trunc) / (16 voxel)) per axis), -1 in the unused
+ * places and for a pixel without depth.  2 sdf_trunc <= 16 voxel is required (at most 2 blocks per axis): LK_ERR_ARG otherwise.
+ *
+ * lk_tsdf_integrate: one workgroup per entry of touched_slots[n_touched] (distinct slots).  Per voxel: (x, y, z) = w2c centre; if z > 0:
+ * u = x fx / z + cx + 0.5, v = y fy / z + cy + 0.5; if 0 <= u < W and 0 <= v < H: pixel ((int)u, (int)v) with depth d; if 0 < d < depth_trunc:
+ * sdf = (d - z) sqrt(xx^2 + yy^2 + 1), xx = ((int)u - cx) / fx, yy = ((int)v - cy) / fy; if sdf > -sdf_trunc: t = min(1, sdf / sdf_trunc),
+ * tsdf <- (tsdf w + t) / (w + 1), r, g, b likewise with floor(clip(c, 0, 1) 255) of color[H, W, 3], w <- w + 1.  Other voxels are not written. */
+int lk_tsdf_touch(const float* depth, int32_t H, int32_t W, const float* host_c2w16, float fx, float fy, float cx, float cy, int32_t stride,
+                  float depth_trunc, float sdf_trunc, float voxel, int64_t* out_keys /*[ceil(H/stride) ceil(W/stride), 8]*/, void* stream);
+int lk_tsdf_integrate(float* planes, const int64_t* slot_keys, int32_t n_slots, const int32_t* touched_slots, int32_t n_touched,
+                      const float* depth, const float* color, int32_t H, int32_t W, const float* host_c2w16, float fx, float fy, float cx,
+                      float cy, float voxel, float sdf_trunc, float depth_trunc, void* stream);
+/* Marching cubes over the blocks, indexed and welded by construction.  The caller sorts the keys: sorted_slots[n_blocks] is the slot of the
+ * block at each position, nbr[n_blocks][8] the position of the block at offset o = dx | dy << 1 | dz << 2 (nbr[.][0] unused), -1 if absent.
+ * The cube of voxel (i, j, k) has its corners c = dx | dy << 1 | dz << 2 at the voxel centres (i + dx, j + dy, k + dz); it is active iff all
+ * eight exist with weight > 0; case bit c = (tsdf < 0).  Edge e = 4 axis + b1 + 2 b2 runs along `axis` from the corner whose other two offsets
+ * are (b1, b2) in ascending axis order; its owner is (block position, voxel) of that lower corner plus the axis.
+ * lk_mc_mark: out_case / out_ntri[n_blocks 4096] = case (0 if inactive) and triangle count of every cube; edge_flag[n_blocks 4096 3] (zeroed by
+ *   the caller) gets a 1 at ((position 4096 + voxel) 3 + axis) of every cut edge of an active cube.
+ * The caller compacts edge_flag (lk_compact_large) into vert_index[V]: vertex ids in (position, voxel, axis) order; and sums out_ntri into
+ *   tri_end[n_blocks 4096] (inclusive).
+ * lk_mc_vertices: vertex v on its edge at p0 + f0 / (f0 - f1) (p1 - p0), out_col the planes r, g, b interpolated alike and divided by 255.
+ * lk_mc_triangles: out_tri[F, 3] = the vertex ids of every active cube's triangles (the generated table csrc/lk_mc_table.h; normals point from
+ *   tsdf < 0 to tsdf >= 0), cube after cube in (position, voxel) order. */
+int lk_mc_mark(const float* planes, const int32_t* sorted_slots, const int32_t* nbr, int32_t n_blocks, uint8_t* out_case, uint8_t* out_ntri,
+               uint8_t* edge_flag, void* stream);
+int lk_mc_vertices(const float* planes, const int64_t* slot_keys, const int32_t* sorted_slots, const int32_t* nbr, int32_t n_blocks,
+                   const int32_t* vert_index, int32_t V, float voxel, float* out_pos /*[V,3]*/, float* out_col /*[V,3]*/, void* stream);
+int lk_mc_triangles(const int32_t* sorted_slots, const int32_t* nbr, int32_t n_blocks, const uint8_t* cube_case, const int32_t* tri_end,
+                    const int32_t* vert_index, int32_t V, int32_t* out_tri /*[F,3]*/, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -226,6 +226,13 @@ class LoopyLib:
                                       C.c_void_p], C.c_int),
             ('lk_ransac_score', [_fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_ransac_best', [_fp, _fp, _fp, _fp, _fp, C.c_uint64, _fp, C.c_void_p], C.c_int),
+            ('lk_tsdf_touch', [_fp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
+                               C.c_float, C.c_float, C.c_float, _fp, C.c_void_p], C.c_int),
+            ('lk_tsdf_integrate', [_fp, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p], C.c_int),
+            ('lk_mc_mark', [_fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_mc_vertices', [_fp, _fp, _fp, _fp, C.c_int32, _fp, C.c_int32, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_mc_triangles', [_fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

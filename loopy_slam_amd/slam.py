@@ -9,7 +9,8 @@
 
 All arithmetic of the hot path runs in libloopyhip (loopy_slam_amd.core / .steps / .optim); what remains here is
 per-frame bookkeeping in torch.  Loop closure's geometric back end (segment registration, pose graph, map correction) is
-loop_closure.py, off by default (cfg['loop_closure']['enabled']); place recognition stays out of scope, as do datasets, meshing and
+loop_closure.py, off by default (cfg['loop_closure']['enabled']); the final mesh (TSDF fusion of the mapped frames + marching
+cubes) is tsdf.py, off by default (cfg['meshing']['enabled']); place recognition stays out of scope, as do datasets and
 visualisation (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
 the default is the gfx950 library on the current CUDA device.
 """
@@ -484,6 +485,12 @@ class Mapper:
         # loop closure (loop_closure.py; off unless cfg['loop_closure']['enabled']): when a segment opens, its candidate pairs are registered,
         # the segment pose graph is optimised and map, poses and keyframes are moved - where the reference calls apply_transformation
         self.closer = loop_closure.LoopCloser(cfg, self.npc, slam) if loop_closure.settings(cfg)['enabled'] else None
+        # final mesh (tsdf.py; off unless cfg['meshing']['enabled'], and then imported at the end of run()): TSDF fusion of the mapped frames
+        self.meshing = bool((cfg.get('meshing') or {}).get('enabled'))
+        self.mesh_file = None
+        if self.meshing and getattr(getattr(slam, 'dist', None), 'world', 1) > 1:
+            raise NotImplementedError('meshing.enabled with world > 1: the fusion runs on one rank - mesh the checkpoint afterwards '
+                                      '(tools/get_mesh_tsdf_fusion.py)')
         self.segment_strategy = m.get('segment_strategy', 'rot_trans')
         self.segment_rot_cos, self.segment_rel_trans = m.get('segment_rot_cos', 0.94), m.get('segment_rel_trans', 0.30)
         self.fixed_segment_size = m.get('fixed_segment_size', 50)
@@ -792,6 +799,9 @@ class Mapper:
             if self.cfg.get('stop') and idx != 0 and idx % self.cfg['stop'] == 0:       # Tracker.py:423, Mapper.py:1048 (run.py --stop)
                 n = idx + 1
                 break
+        if self.meshing:                        # Mapper.py:1080-1200: re-render the mapped frames, fuse them, write the mesh
+            from . import tsdf
+            self.mesh_file, _ = tsdf.mesh_run(self, n)
         return slam.estimate_c2w_list[:n], slam.gt_c2w_list[:n]
 
 
