@@ -672,6 +672,52 @@ int lk_mc_vertices(const float* planes, const int64_t* slot_keys, const int32_t*
 int lk_mc_triangles(const int32_t* sorted_slots, const int32_t* nbr, int32_t n_blocks, const uint8_t* cube_case, const int32_t* tri_end,
                     const int32_t* vert_index, int32_t V, int32_t* out_tri /*[F,3]*/, void* stream);
 
+/* ---------------------------------------------------------------- reconstruction evaluation
+ * What the reference runs on the host at the end of an experiment (src/tools/cull_mesh.py, src/tools/eval_recon.py around trimesh, Open3D and
+ * scipy's cKDTree).  fp32 except the sampler's cumulative area table; the only atomic is the z-buffer's unsigned integer minimum: equal inputs
+ * and an equal seed give equal bits.
+ *
+ * lk_nearest: for every query of queries[P,3] the nearest point of the index under the contract distance d2 = (dx dx + dy dy) + dz dz (each
+ * operation rounded once), order (d2, index): out_d2[P] and out_idx[P].  max_dist = +infinity: the minimum over ALL indexed points, wherever the
+ * query lies (the search box doubles from one cell edge until the hit lies inside the half-width searched or the box covers the grid).  Finite
+ * max_dist: candidates are the points with d2 <= fl(max_dist * max_dist); a query without one gets index -1 and d2 = +infinity, as does every
+ * query of an empty index. */
+int lk_nearest(lk_knn_t knn, const float* queries, int64_t P, float max_dist, float* out_d2, int32_t* out_idx, void* stream);
+/* lk_mesh_areas: out_area[f] = 0.5 sqrt((cx cx + cy cy) + cz cz), c = (v1 - v0) x (v2 - v0) with every difference, product and difference of
+ * products rounded once; 0 for a face with an index outside [0, V) or a non-finite area.
+ * lk_mesh_sample: sample s = 0 .. S of `seed`: (r0, r1, r2, r3) = Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (s, 0, 0, 0) (the rounds are written out at lk_ransac_hypotheses).  Face: the first f with cum_area[f] > ((r0 + 0.5) 2^-32)
+ * cum_area[F - 1] in fp64, by bisection - cum_area[F] is the inclusive running sum of the areas in fp64, the caller's; it must end above 0;
+ * a zero-area face is never chosen.  Point: u_k = fl(fl((float)r_k + 0.5) 2^-32), a = sqrt(u_1), b = u_2, barycentrics (w0, w1, w2) = (1 - a,
+ * a (1 - b), a b), every operation rounded once; out_pos = fma(w0, v0, fma(w1, v1, w2 v2)) per coordinate.  out_face[S], out_bary[S,3]. */
+int lk_mesh_areas(const float* verts, int64_t V, const int32_t* faces, int64_t F, float* out_area, void* stream);
+int lk_mesh_sample(const float* verts, int64_t V, const int32_t* faces, int64_t F, const double* cum_area, uint64_t seed, int64_t S,
+                   float* out_pos /*[S,3]*/, int32_t* out_face /*[S]*/, float* out_bary /*[S,3]*/, void* stream);
+/* lk_mesh_cull: seen[i] = 1 if points[i] projects into the image of at least one of the n_poses cameras; bytes of unseen points are NOT written
+ * (the caller zeroes them; a long trajectory goes through in chunks that OR into the same bytes).  w2c[n_poses][12]: DEVICE memory, row-major
+ * 3 x 4 inverses of the project's camera-to-world matrices (x right, y up, looking down -z), inverted by the caller.  Per pose, with (x, y, z) =
+ * w2c p by three fused multiply-adds per coordinate (lk_icp_accumulate) and the reference's signs: zz = z + 1e-5, u = (fx (-x) + cx z) / zz,
+ * v = (fy y + cy z) / zz; seen iff 0 <= -zz and 0 < u < W and 0 < v < H. */
+int lk_mesh_cull(const float* points, int64_t N, const float* w2c, int32_t n_poses, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                 uint8_t* seen, void* stream);
+/* Depth image of a triangle mesh: depth[i][j] = the smallest z in [near, far] at which the line through the camera centre with direction
+ * ((j - cx) / fx, (i - cy) / fy, 1) (camera axes x right, y down, z forward) meets a triangle, either face; 0 where it meets none.
+ * host_w2c12: HOST pointer, row-major 3 x 4 world -> that camera.  Per triangle with camera-space corners a, b, c the pixel is inside iff its
+ * direction d has d . (b x c), d . (c x a), d . (a x b) all >= 0 or all <= 0 - p x q evaluated as (p - q) x q with the corners of the edge in
+ * ascending vertex order and negated for the reverse edge, so that two triangles sharing an edge agree on it bit for bit - and then
+ * z = (n . a) / (n . d), n = (b - a) x (c - a).  Nothing is projected for the test, so a triangle crossing the camera plane needs no clipping.
+ * lk_mesh_depth_setup fills depth with the empty pattern, writes the records out_rec[F][16] and, per triangle, the box of 8 x 8-pixel tiles
+ * out_box[F][4] = (first tile column, first tile row, columns, rows) that holds its projection cut at z = near, and out_ntiles[F] = columns x
+ * rows (0 for a triangle wholly nearer than near, beyond far, outside the image, or with a bad index).  The caller forms tile_end[F] = the
+ * inclusive running sum of out_ntiles (T = its last entry, < 2^31).  lk_mesh_depth_raster gives every tile of that work list one 64-lane
+ * wave - a triangle over the whole image is T waves, not one lane's loop - which takes an unsigned 32-bit atomic minimum on the bit pattern of
+ * the (positive) depth per covered pixel, and then turns the empty pattern into 0. */
+int lk_mesh_depth_setup(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* host_w2c12, int32_t H, int32_t W, float fx,
+                        float fy, float cx, float cy, float near, float far, float* out_rec, int32_t* out_box, int32_t* out_ntiles,
+                        float* out_depth /*[H,W]*/, void* stream);
+int lk_mesh_depth_raster(const float* rec, const int32_t* box, const int32_t* tile_end, int64_t F, int64_t T, int32_t H, int32_t W, float fx,
+                         float fy, float cx, float cy, float near, float far, float* depth /*[H,W]*/, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -233,6 +233,15 @@ class LoopyLib:
             ('lk_mc_mark', [_fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_mc_vertices', [_fp, _fp, _fp, _fp, C.c_int32, _fp, C.c_int32, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_mc_triangles', [_fp, _fp, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, C.c_void_p], C.c_int),
+            ('lk_nearest', [C.c_void_p, _fp, C.c_int64, C.c_float, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_mesh_areas', [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_void_p], C.c_int),
+            ('lk_mesh_sample', [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_uint64, C.c_int64, _fp, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_mesh_cull', [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _fp,
+                              C.c_void_p], C.c_int),
+            ('lk_mesh_depth_setup', [_fp, C.c_int64, _fp, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_mesh_depth_raster', [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_float, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)
