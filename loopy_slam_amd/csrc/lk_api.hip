@@ -140,7 +140,7 @@ extern "C" int64_t lk_render_act_floats(int32_t R, int32_t S, uint32_t flags) {
 
 // ------------------------------------------------------------------ backward scratch layout
 namespace {
-struct BwdLayout { int64_t dfeat, d_raw, dc_geo, dc_col, dp_embed, dp_embed_col, dp_rel, dp_total, dw_rel, w_eff, dlogit, aff_part, part_bg, part_br, hbar, w_sum, dy_col, rows, dw1_part, dw2_part, wg_part, geo_part, seg_rank, seg_list, total; };
+struct BwdLayout { int64_t dfeat, d_raw, dc_geo, dc_col, dp_embed, dp_embed_col, dp_rel, dp_total, dw_rel, w_eff, dlogit, aff_part, part_bg, part_br, hbar, w_sum, dy_col, rows, dw1_part, dw2_part, wg_part, geo_part, seg_rank, seg_list, seg_tmp, total; };
 BwdLayout bwd_layout(int64_t P, uint32_t flags) {
     BwdLayout L;
     int64_t o = 0;
@@ -173,6 +173,7 @@ BwdLayout bwd_layout(int64_t P, uint32_t flags) {
     L.geo_part = o; if (gw && (flags & LK_FLAG_GRAD_GEO_DECODER)) o += al(lk_geo_wgrad_part_floats((int)P));
     L.seg_rank = o; if (flags & LK_FLAG_GRAD_FEATS) o += al(8 * P);
     L.seg_list = o; if (flags & LK_FLAG_GRAD_FEATS) o += al(8 * P);
+    L.seg_tmp = o; if (flags & LK_FLAG_GRAD_FEATS) o += al(8 * P);
     L.total = o;
     return L;
 }
@@ -429,6 +430,7 @@ static void seg_args(const lk_render_desc* d, int P, LkFeatScatterArgs& fs) {
     fs.P = P; fs.min_nn = d->min_nn; fs.nbr_idx = d->nbr_idx; fs.nbr_w = d->nbr_w; fs.nbr_count = d->nbr_count;
     fs.row_mask = d->grad_row_mask; fs.seg_cnt = d->knn->seg_cnt; fs.seg_off = d->knn->seg_off; fs.seg_sums = d->knn->seg_sums; fs.N = (int)d->knn->n;
     fs.seg_rank = reinterpret_cast<int32_t*>(d->bwd_scratch + L.seg_rank); fs.seg_list = reinterpret_cast<int32_t*>(d->bwd_scratch + L.seg_list);
+    fs.seg_tmp = reinterpret_cast<int32_t*>(d->bwd_scratch + L.seg_tmp);
 }
 static int seg_sort_async(const lk_render_desc* d, int P, bool counted, hipStream_t st) {
     LkFeatScatterArgs fs;

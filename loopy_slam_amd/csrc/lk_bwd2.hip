@@ -140,15 +140,28 @@ __global__ __launch_bounds__(256) void k_interp_bwd_x(LkInterpBwdArgs a, Exposur
 // neighbours = 197 k rows on 15 k points of the benchmark frame: 12.7 rows per point), and the atomic scatter pays for every
 // row twice (two tables) at the memory-side atomic rate, with the adds of a point serialised on its line.  The rows are
 // counting-sorted by point - k_seg_count (counts, and an atomic rank of the row among the rows of its point; inside k_sample_interp
-// when the forward knows that this backward follows), an exclusive scan of the per-point counts that also clears them, k_seg_place,
-// then k_seg_rank_det (the rank becomes the number of the point's rows with a smaller row index) and k_seg_place again, so that the
-// list is ordered by (point, row) in every run - which only needs the neighbour indices: it runs on the second stream beside the
-// decoders.
-// k_feat_gather then gives every half-wave (32 channels) 16 consecutive rows of the sorted list; a point belongs to the half-wave
+// when the forward knows that this backward follows), an exclusive scan of the per-point counts that also clears them, k_seg_place
+// into a scratch list (seg_tmp: a point's rows in the order of their atomic ranks) and k_seg_order, which moves every entry to the
+// place its row index gives it among the rows of its point, so that the list is ordered by (point, row) in every run - which only
+// needs the neighbour indices: it runs on the second stream beside the decoders.
+// k_feat_gather then gives every half-wave (32 channels) 16 consecutive entries of the sorted list; a point belongs to the half-wave
 // whose chunk holds its first row, which adds all of the point's rows in registers in list order - past its chunk's end if the run
-// goes on - and flushes them with ONE atomic per point, so the sums repeat bit for bit (about 27 k flushes instead of 197 k).  A
-// half-wave's work is its chunk plus the tail of its last point's run: a per-point linked list walked by its first row, with every
-// point's whole chain on one half-wave, was slower than the atomics (the longest chain sets the time).
+// goes on - and flushes them with ONE atomic per point and table, so the sums repeat bit for bit (about 27 k flushes instead of
+// 197 k).  A half-wave's time is a chain of memory round trips, not bandwidth, so the walk keeps the chain short:
+//   - the list is read in windows of 32 entries, one per lane: row, then point and weight of the row - two dependent round trips per
+//     32 rows; comparing every lane's point with its left neighbour's (lane 0: the entry in front of the window) and ORing the
+//     result over the half gives the run starts as a bit mask.  The first run start inside the chunk is where the half-wave begins
+//     (none: the chunk lies inside another half-wave's run, and it returns), the first one at or behind the chunk's end is where
+//     it stops, the others are the flushes in between;
+//   - the values (d c rows or d feat rows) of eight rows at a time are fetched back to back, row and weight broadcast from the lane
+//     that holds them, and only then added, one by one in list order.  Which tables there are is a template argument of the walk
+//     (feat_walk<MODE>): as a run-time choice inside the loop it put a wait behind every row's load on two of the three paths;
+//   - a sum that is finished inside a batch is set aside and flushed behind the batch's last add.  The memory counter retires in order
+//     and the compiler counts an atomic in a branch as "maybe none", so a wait for a value behind a flush waited for the flush as well
+//     (600 to 3 000 cycles) - a batch took a load's latency PLUS an atomic's.  Now every value has arrived before the first atomic is
+//     issued, the next batch's loads follow the atomics at once, and the two latencies overlap.
+// (A per-point linked list walked by its first row, with every point's whole chain on one half-wave, was slower than the atomics:
+// the longest chain sets the time.)
 __global__ __launch_bounds__(256) void k_seg_count(LkFeatScatterArgs a) {
     const long long row = (long long)blockIdx.x * 256 + (int)threadIdx.x;
     if (row >= (long long)a.P * LK_K) return;
@@ -178,25 +191,29 @@ __global__ __launch_bounds__(256) void k_seg_place(LkFeatScatterArgs a) {
     if (row == 0 && a.seg_total) a.seg_total[y] = off[a.N];
 }
 
-// The count pass hands out ranks with an atomic, so the order of a point's rows in the list changed from run to run, and with it the order
-// in which k_feat_gather adds them.  This pass replaces the rank by the number of rows of the same point with a smaller row index, and
-// k_seg_place runs again: the list is sorted by (point, row) every run.
-__global__ __launch_bounds__(256) void k_seg_rank_det(LkFeatScatterArgs a) {
-    const long long row = (long long)blockIdx.x * 256 + (int)threadIdx.x;
-    if (row >= (long long)a.P * LK_K) return;
+// The count pass hands out ranks with an atomic, so the order of a point's rows in the list k_seg_place writes changes from run to run, and
+// with it the order in which k_feat_gather would add them.  That list is therefore a scratch (seg_tmp), and this pass writes the final
+// one: entry i of the scratch goes to the start of its point's segment plus the number of the segment's rows with a smaller row index, so
+// seg_list is sorted by (point, row) in every run.  One thread per list ENTRY, not per row: neighbouring threads are in the same segment
+// and scan the same few cache lines of the scratch.
+__global__ __launch_bounds__(256) void k_seg_order(LkFeatScatterArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + (int)threadIdx.x;
     const int y = (int)blockIdx.y;
-    const long long base = (long long)y * a.P * LK_K;
-    if (a.seg_rank[base + row] < 0) return;
     const int32_t* __restrict__ off = a.seg_off + (size_t)y * a.cnt_stride;
+    if (i >= off[a.N]) return;                               // (the list holds at most 8P entries: the grid covers them)
+    const long long base = (long long)y * a.P * LK_K;
+    const int32_t* __restrict__ tmp = a.seg_tmp + base;
+    const int row = tmp[i];
     const int idx = a.nbr_idx[base + row];
     const int key = a.key_of ? a.key_of[idx] : idx;
+    const int s = off[key], e = off[key + 1];
     int rk = 0;
-    for (int i = off[key], e = off[key + 1]; i < e; ++i) rk += a.seg_list[base + i] < (int)row;
-    a.seg_rank[base + row] = rk;
+    for (int j = s; j < e; ++j) rk += tmp[j] < row;
+    a.seg_list[base + s + rk] = row;
 }
 
 // linear2 of the rel-pos MLP (see k_dw2_hbar below) as a body: block bx of nb.  LDS for 32 samples at a time (20 KB: as a rider of k_feat_gather
-// it must not cost that kernel its eight workgroups per compute unit), a block's 64 samples in two passes.
+// it sets that launch's LDS - with the other riders 39.5 KB and 106 VGPRs, four workgroups per compute unit), a block's 64 samples in two passes.
 #define LK_DW2_LDS_SAMPLES 32
 __device__ __forceinline__ void dw2_body(const float* __restrict__ dc, const float* __restrict__ w_sum, const float* __restrict__ hbar,
                                          int P_all, const int32_t* __restrict__ live_rays, int S, float* __restrict__ part, int bx, int nb) {
@@ -246,8 +263,95 @@ __device__ __forceinline__ void dw2_body(const float* __restrict__ dc, const flo
     if (k0 == 0) out[128] = bsum;
 }
 #define LK_GATHER_CHUNK 16
+#define LK_GATHER_WINDOW 32      // list entries whose row, point and weight a half-wave fetches at once, one per lane
+#define LK_GATHER_BATCH 8        // rows whose values are in flight together
 __device__ __forceinline__ void col_reduce_body(const float* __restrict__ part, int n_parts, int width, float* __restrict__ out, int bx, float (*sh)[32],
                                                 const LkStepRider& sr);
+// the walk of one half-wave over its chunk of the sorted list.  MODE names the tables, so that the loop over a batch's rows has no branch
+// between its loads: 0 geometry rows only, 1 colour rows w * d c_col as well, 2 colour rows d feat (rel-pos)
+__device__ __forceinline__ void lk_arrived(float v) { asm volatile("" : : "v"(v)); }      // a use of v: the wait for its load stands here
+template <int MODE>
+__device__ __forceinline__ void feat_walk(const LkFeatScatterArgs& a, int bx) {
+    constexpr bool col = MODE != 0;
+    const int c = (int)threadIdx.x & 31;
+    const long long i0l = ((long long)bx * 8 + ((int)threadIdx.x >> 5)) * LK_GATHER_CHUNK;
+    const int total = a.seg_total ? *a.seg_total : a.seg_off[a.N];
+    if (i0l >= total) return;
+    // every point is summed by the half-wave whose chunk holds its first row, in list order, and flushed with ONE atomic: a point whose
+    // rows ran over chunk boundaries took three or more atomics, and their order (the sum's rounding) changed from run to run
+    const int i0 = (int)i0l, e = min(i0 + LK_GATHER_CHUNK, total);
+    const float* __restrict__ tab_c = MODE == 2 ? a.dfeat : a.dc_col;      // the colour rows' values: one row per list row, or per sample
+    int cur = -1, carry = -1;                      // carry: the point of the entry in front of the window
+    float sg = 0.0f, sc = 0.0f;
+    for (int wb = i0;; wb += LK_GATHER_WINDOW) {
+        // the window's list entries, one per lane: row, then point and weight of the row (two round trips for 32 rows); lanes past the
+        // list's end read its last entry.  In the first window lane 0 also fetches the entry in front of the chunk.
+        const int row = a.seg_list[min(wb + c, total - 1)];
+        const int before = (wb == i0 && c == 0 && i0 > 0) ? a.seg_list[i0 - 1] : -1;
+        const int pt = a.nbr_idx[row];
+        const float w = a.nbr_w[row];
+        if (before >= 0) carry = a.nbr_idx[before];
+        int prev = __shfl_up(pt, 1, 32);
+        if (c == 0) prev = carry;
+        // bit u of m: entry wb + u starts a run, or lies past the list's end (ORed over the half with shuffles: the two halves of a wave
+        // are at different windows, a ballot is the wave's)
+        unsigned m = (wb + c >= total || pt != prev) ? 1u << c : 0u;
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) m |= __shfl_xor(m, o, 32);
+        int u0 = 0;
+        if (wb == i0) {                            // head: the first run that starts inside the chunk (none: the chunk lies inside another's run)
+            const unsigned head = m & ((1u << (e - i0)) - 1u);
+            if (!head) return;
+            u0 = __builtin_ctz(head);
+        }
+        // the walk ends at the first run start at or behind the chunk's end
+        const unsigned tail = wb == i0 ? m & ~((1u << (e - i0)) - 1u) : m;
+        const int u1 = tail ? __builtin_ctz(tail) : LK_GATHER_WINDOW;
+        for (int ub = u0; ub < u1; ub += LK_GATHER_BATCH) {      // the values of a batch of rows: independent loads, then the adds in list order
+            float vg[LK_GATHER_BATCH], vc[LK_GATHER_BATCH], wr[LK_GATHER_BATCH];
+#pragma unroll
+            for (int k = 0; k < LK_GATHER_BATCH; ++k) {            // (a short last batch reads its last row again: a fixed number of loads in
+                const int uu = min(ub + k, u1 - 1);                //  flight lets the compiler wait for each value by its place in the counter)
+                const int r = __shfl(row, uu, 32);
+                wr[k] = __shfl(w, uu, 32);
+                const size_t s = (size_t)(r >> 3) * LK_C + c;
+                vg[k] = a.dc_geo[s];
+                if (col) vc[k] = tab_c[MODE == 2 ? (size_t)r * LK_C + c : s];
+            }
+            // the adds, in list order.  A sum that is finished here is set aside (fp: its point, -1: none) and flushed behind the batch's last
+            // add: an atomic issued between the adds would be waited for with the next value (see above)
+            int fp[LK_GATHER_BATCH];
+            float fg[LK_GATHER_BATCH], fc[LK_GATHER_BATCH];
+#pragma unroll
+            for (int k = 0; k < LK_GATHER_BATCH; ++k) {
+                const int u = ub + k;
+                const int pu = __shfl(pt, min(u, LK_GATHER_WINDOW - 1), 32);
+                fp[k] = -1; fg[k] = 0.0f; fc[k] = 0.0f;
+                if (u >= u1) continue;
+                if ((m >> u) & 1u) {
+                    fp[k] = cur; fg[k] = sg; fc[k] = sc;
+                    cur = pu; sg = 0.0f; sc = 0.0f;
+                }
+                sg += wr[k] * vg[k];
+                if (col) sc += MODE == 1 ? wr[k] * vc[k] : vc[k];
+            }
+            lk_arrived(vg[LK_GATHER_BATCH - 1]);   // (a short batch adds fewer rows than it loaded)
+            if (col) lk_arrived(vc[LK_GATHER_BATCH - 1]);
+#pragma unroll
+            for (int k = 0; k < LK_GATHER_BATCH; ++k)
+                if (fp[k] >= 0) {
+                    atomicAdd(a.g_geo_feats + (size_t)fp[k] * LK_C + c, fg[k]);
+                    if (col) atomicAdd(a.g_col_feats + (size_t)fp[k] * LK_C + c, fc[k]);
+                    if (a.act_flag && c == 0) a.act_flag[fp[k]] = 1;
+                }
+        }
+        if (tail) break;
+        carry = __shfl(pt, LK_GATHER_WINDOW - 1, 32);
+    }
+    atomicAdd(a.g_geo_feats + (size_t)cur * LK_C + c, sg);
+    if (col) atomicAdd(a.g_col_feats + (size_t)cur * LK_C + c, sc);
+    if (a.act_flag && c == 0) a.act_flag[cur] = 1;
+}
 __global__ __launch_bounds__(256) void k_feat_gather(LkFeatScatterArgs a) {
     // rider, FIRST in the grid: linear2 of the rel-pos MLP (k_dw2_hbar's blocks; it reads what the rel-pos backward left, as the gather does) -
     // as a launch of its own behind the gather it ran alone on the chip for 16 us of every 'color' iteration
@@ -264,55 +368,9 @@ __global__ __launch_bounds__(256) void k_feat_gather(LkFeatScatterArgs a) {
         col_reduce_body(a.red_part, a.red_n, a.red_width, a.red_out, bx - a.red_block0, sh, none);
         return;
     }
-    const int c = (int)threadIdx.x & 31;
-    long long i0 = ((long long)bx * 8 + ((int)threadIdx.x >> 5)) * LK_GATHER_CHUNK;
-    const int total = a.seg_total ? *a.seg_total : a.seg_off[a.N];
-    if (i0 >= total) return;
-    // every point is summed by the half-wave whose chunk holds its first row, in list order, and flushed with ONE atomic: a point whose
-    // rows ran over chunk boundaries took three or more atomics, and their order (the sum's rounding) changed from run to run
-    const long long e = min(i0 + LK_GATHER_CHUNK, (long long)total);
-    if (i0 > 0) {
-        const int prev = a.nbr_idx[a.seg_list[i0 - 1]];
-        while (i0 < e && a.nbr_idx[a.seg_list[i0]] == prev) ++i0;
-        if (i0 == e) return;
-    }
-    // the chunk's rows, then - four at a time, no separate scan for the run's end - the rest of the run of the chunk's last point
-    const bool col = a.dfeat != nullptr || a.dc_col != nullptr;
-    int cur = -1;
-    float sg = 0.0f, sc = 0.0f;
-    for (long long b = i0; b < total; b += 4) {               // four rows per step: their loads are independent
-        int row[4], idx[4];
-        float vg[4], vc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) row[u] = a.seg_list[min(b + u, (long long)total - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            idx[u] = a.nbr_idx[row[u]];
-            const float w = a.nbr_w[row[u]];
-            const int s = row[u] >> 3;
-            vg[u] = w * a.dc_geo[(size_t)s * LK_C + c];
-            vc[u] = a.dfeat ? a.dfeat[(size_t)row[u] * LK_C + c] : (a.dc_col ? w * a.dc_col[(size_t)s * LK_C + c] : 0.0f);
-        }
-        bool done = false;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (done || b + u >= total) { done = true; continue; }
-            if (idx[u] != cur) {
-                if (b + u >= e) { done = true; continue; }     // past the chunk: only the run of its last point goes on
-                if (cur >= 0) {
-                    atomicAdd(a.g_geo_feats + (size_t)cur * LK_C + c, sg);
-                    if (col) atomicAdd(a.g_col_feats + (size_t)cur * LK_C + c, sc);
-                    if (a.act_flag && c == 0) a.act_flag[cur] = 1;
-                }
-                cur = idx[u]; sg = 0.0f; sc = 0.0f;
-            }
-            sg += vg[u]; sc += vc[u];
-        }
-        if (done) break;
-    }
-    atomicAdd(a.g_geo_feats + (size_t)cur * LK_C + c, sg);
-    if (col) atomicAdd(a.g_col_feats + (size_t)cur * LK_C + c, sc);
-    if (a.act_flag && c == 0) a.act_flag[cur] = 1;
+    if (a.dfeat) feat_walk<2>(a, bx);
+    else if (a.dc_col) feat_walk<1>(a, bx);
+    else feat_walk<0>(a, bx);
 }
 
 __global__ __launch_bounds__(256) void k_rays_bwd(LkRaysBwdArgs a) {
@@ -1461,9 +1519,10 @@ int lk_launch_seg_sort(const LkFeatScatterArgs& a, bool counted, hipStream_t st,
     // seg_cnt is zero on entry: the scan of the previous sort cleared what that sort had counted
     if (!counted) hipLaunchKernelGGL(k_seg_count, dim3(nb, batch), dim3(256), 0, st, a);
     lk_launch_scan_i32(a.seg_cnt, a.seg_off, a.seg_sums, a.N + 1, st, batch, a.cnt_stride, a.sums_stride);
-    hipLaunchKernelGGL(k_seg_place, dim3(nb, batch), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_seg_rank_det, dim3(nb, batch), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_seg_place, dim3(nb, batch), dim3(256), 0, st, a);
+    LkFeatScatterArgs t = a;
+    t.seg_list = a.seg_tmp;                                  // in atomic-rank order: a scratch
+    hipLaunchKernelGGL(k_seg_place, dim3(nb, batch), dim3(256), 0, st, t);
+    hipLaunchKernelGGL(k_seg_order, dim3(nb, batch), dim3(256), 0, st, a);
     return LK_OK;
 }
 int lk_launch_rays_bwd(const LkRaysBwdArgs& a, hipStream_t st) {

@@ -239,7 +239,8 @@ struct LkFeatScatterArgs {
     int32_t* seg_off;                              // [N + 1] (lk_knn_s::seg_off) exclusive offsets of the points' rows; [N] = rows in the list
     int32_t* seg_sums;                             // scan scratch (lk_knn_s::seg_sums)
     int32_t* seg_rank;                             // [8P] rank of the row among the rows of its point, -1 = row takes no part
-    int32_t* seg_list;                             // [8P] rows ordered by point
+    int32_t* seg_list;                             // [8P] rows ordered by point, a point's rows by row index
+    int32_t* seg_tmp;                              // [8P] (per batch member) sort scratch: the rows by point in the order of their atomic ranks
     int32_t* seg_total;                            // [1] number of rows in seg_list, written by k_seg_place (NULL: seg_off[N])
     // a batch of sorts in one launch (blockIdx.y; lk_map_frame sorts the rows of several iterations ahead of its loop): member y reads
     // nbr_* / live_rays / seg_total of iteration y (consecutive arrays) and uses seg_cnt / seg_off + y * cnt_stride, seg_sums + y * sums_stride

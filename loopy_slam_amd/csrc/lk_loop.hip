@@ -264,7 +264,7 @@ TrackWork track_work(int64_t R, int64_t S, int64_t iters) {
     w.total = o;
     return w;
 }
-struct MapWork { int64_t rays_o, rays_d, gt_depth, gt_color, r2_ray, thr, n_live, frame_id, z, nbr_idx, nbr_w, nbr_count, seg_list, seg_total, seg_rank, w_next, loss_rows, c_col_alt, total; };
+struct MapWork { int64_t rays_o, rays_d, gt_depth, gt_color, r2_ray, thr, n_live, frame_id, z, nbr_idx, nbr_w, nbr_count, seg_list, seg_total, seg_rank, w_next, loss_rows, c_col_alt, seg_tmp, total; };
 MapWork map_work(int64_t R, int64_t S, int64_t iters) {
     MapWork w;
     int64_t o = 0;
@@ -295,6 +295,7 @@ MapWork map_work(int64_t R, int64_t S, int64_t iters) {
     // rewrites it a few microseconds into the next iteration).  With two, iteration it + 2 is the next writer of iteration it's buffer, and
     // it starts behind the join of iteration it + 1, which is behind iteration it's k_wgrad on the side stream.
     w.c_col_alt = o; o += al4(P * LK_C);
+    w.seg_tmp = o; o += al4(P * LK_K * LK_SEG_BATCH);         // the sort's scratch list, as seg_rank for the iterations of one launch
     w.total = o;
     return w;
 }
@@ -633,7 +634,7 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
             fs.nbr_count = reinterpret_cast<int32_t*>(W0 + wk.nbr_count) + (size_t)it * Pn;
             fs.seg_cnt = kn->seg_cnt; fs.seg_off = kn->seg_off; fs.seg_sums = kn->seg_sums;
             fs.cnt_stride = kn->seg_stride; fs.sums_stride = kn->seg_sums_stride;
-            fs.seg_rank = reinterpret_cast<int32_t*>(W0 + wk.seg_rank);
+            fs.seg_rank = reinterpret_cast<int32_t*>(W0 + wk.seg_rank); fs.seg_tmp = reinterpret_cast<int32_t*>(W0 + wk.seg_tmp);
             fs.seg_list = reinterpret_cast<int32_t*>(W0 + wk.seg_list) + (size_t)it * Pn * LK_K;
             fs.seg_total = reinterpret_cast<int32_t*>(W0 + wk.seg_total) + it;
             fs.live_rays = reinterpret_cast<const int32_t*>(W0 + wk.n_live) + it; fs.S = d->render.S;
