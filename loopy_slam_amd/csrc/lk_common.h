@@ -392,6 +392,21 @@ __device__ __forceinline__ float lk_half_wave_sum(float v) {
     return v;
 }
 
+// Sum over a workgroup of NW waves, the same value in every thread: wave sums by shuffles, then added left to right (a fixed order).
+// sh: NW floats of LDS; the barrier in front makes it reusable from one call to the next.  All threads of the workgroup call.
+template <int NW>
+__device__ __forceinline__ float lk_block_sum(float v, float* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if (lk_lane() == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = sh[0];
+#pragma unroll
+    for (int i = 1; i < NW; ++i) s += sh[i];
+    return s;
+}
+
 // sum over the 8 lanes of an aligned 8-group (the 8 neighbour rows of a sample): every lane gets the total
 template <bool PIN = false>
 __device__ __forceinline__ float lk_sum8(float v) {

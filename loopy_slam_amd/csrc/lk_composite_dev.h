@@ -1,11 +1,30 @@
 // Per-ray alpha composite and its backward as device functions (raw2outputs_nerf_color, src/common.py:382-422;
-// Renderer.py:184-200), shared by the many-workgroup kernels (k_composite, k_composite_bwd) and the one-workgroup
-// fused forms of the tracking loop (lk_loop.hip).
+// Renderer.py:184-200), shared by the one-thread-per-ray kernels (k_composite, k_composite_bwd, k_track_composite,
+// k_loss_mapper_exposure), the epilogue of the tracker's fused forward (k_relpos_decode_fwd) and the one-lane-per-sample
+// prologues of k_decode_bwd (lk_map_draw, lk_cb_draw; lk_track_draw in lk_track_dev.h).
 #pragma once
 #include "lk_common.h"
 #include "lk_kernels.h"
+#include "lk_loss_dev.h"
 
 struct LkRayOut { float depth, var, c0, c1, c2; bool valid; };
+// the ray's outputs into the buffers of a (LkCompositeArgs or LkTrackLossArgs)
+template <class Args>
+__device__ __forceinline__ void lk_store_ray_out(const Args& a, int r, const LkRayOut& o) {
+    a.depth[r] = o.depth; a.var[r] = o.var;
+    a.color[3 * r] = o.c0; a.color[3 * r + 1] = o.c1; a.color[3 * r + 2] = o.c2;
+    a.valid_ray[r] = o.valid ? 1 : 0;
+}
+// float4 o = out[s_own], with constant indices only (a variable index would put the array into scratch memory).  A macro and not a
+// function, and lk_map_draw below spells the mapper's loss and its stores out, for one reason: both are in the prologue of k_decode_bwd, whose
+// register allocation reacts to the smallest change of the code in front of it - behind a function the same three lines moved its
+// instantiations by -35 ... +300 instructions, lk_map_ray_loss called from lk_map_draw added 22 scalar spills to <true, true, true>
+// (profiles/loss_forms.md).  As they stand the kernel's instruction stream is what it was.
+#define LK_PICK_SAMPLE(o, out, s_own)        \
+    float4 o = out[0];                       \
+    _Pragma("unroll")                        \
+    for (int s = 1; s < LK_S_MAX; ++s)       \
+        if (s == s_own) o = out[s];
 
 // occupancy of unsupported samples := -100, alpha composite, depth / variance / colour, validity (decoder.py:259-260); q = raw rows of the
 // ray's samples, has = the sample has its neighbours, z = its depth along the ray
@@ -149,16 +168,13 @@ __device__ __forceinline__ float4 lk_composite_bwd_sample(const float* __restric
                                                           float gt_depth, float d_depth, float gvar, float g0, float g1, float g2) {
     float4 out[LK_S_MAX];
     lk_composite_bwd_ray_core(raw_, zbuf, nbr_count, r, S, min_nn, coef, gt_depth, d_depth, gvar, g0, g1, g2, out);
-    float4 o = out[0];
-#pragma unroll
-    for (int s = 1; s < LK_S_MAX; ++s)
-        if (s == s_own) o = out[s];
+    LK_PICK_SAMPLE(o, out, s_own)
     return o;
 }
 
-// The mapper's loss (Mapper.py:691-720) of the ray of sample sp and the composite backward of it for that sample - k_composite's arithmetic (forward,
-// mask, terms, gradients) with the ray recomputed by the sample's own lane.  write_ray: this lane also stores the ray's outputs (one lane per ray does);
-// *geo / *col / *cnt: the ray's terms of the loss row.
+// The mapper's loss of the ray of sample sp and the composite backward of it for that sample, with the ray recomputed by the sample's own
+// lane.  The loss terms are lk_map_ray_loss's (lk_loss_dev.h), WRITTEN OUT (see LK_PICK_SAMPLE): a change there is a change here, and
+// tests/test_loss_forms.py::test_mapper_inside_the_decoder_backward compares the two bit for bit.  write_ray: this lane also stores the ray's outputs (one lane per ray does); *geo / *col / *cnt: the ray's terms of the loss row.
 __device__ __forceinline__ float4 lk_map_draw(const LkCompositeArgs& a, int sp, bool write_ray, float* geo, float* col, float* cnt) {
     const int S = a.S;
     const int r = sp / S, s_own = sp - r * S;
@@ -176,9 +192,9 @@ __device__ __forceinline__ float4 lk_map_draw(const LkCompositeArgs& a, int sp, 
         if (a.use_color) {
             const float e0 = st.col0 - a.gt_color[3 * r], e1 = st.col1 - a.gt_color[3 * r + 1], e2 = st.col2 - a.gt_color[3 * r + 2];
             l_col = fabsf(e0) + fabsf(e1) + fabsf(e2);
-            d0 = a.w_color * ((e0 > 0.0f) ? 1.0f : ((e0 < 0.0f) ? -1.0f : 0.0f));
-            d1 = a.w_color * ((e1 > 0.0f) ? 1.0f : ((e1 < 0.0f) ? -1.0f : 0.0f));
-            d2 = a.w_color * ((e2 > 0.0f) ? 1.0f : ((e2 < 0.0f) ? -1.0f : 0.0f));
+            d0 = a.w_color * lk_sgn(e0);
+            d1 = a.w_color * lk_sgn(e1);
+            d2 = a.w_color * lk_sgn(e2);
         }
     }
     if (write_ray) {
@@ -191,10 +207,7 @@ __device__ __forceinline__ float4 lk_map_draw(const LkCompositeArgs& a, int sp, 
     *geo = l_geo; *col = l_col; *cnt = l_cnt;
     float4 out[LK_S_MAX];
     lk_ray_grad(st, S, a.coef, gd, dd, 0.0f, d0, d1, d2, out);
-    float4 o = out[0];
-#pragma unroll
-    for (int s = 1; s < LK_S_MAX; ++s)
-        if (s == s_own) o = out[s];
+    LK_PICK_SAMPLE(o, out, s_own)
     return o;
 }
 

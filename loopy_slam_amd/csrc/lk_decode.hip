@@ -794,13 +794,10 @@ __global__ __launch_bounds__(512) void k_relpos_decode_fwd(LkRelposArgs ra, LkDe
 #pragma unroll
             for (int s = 0; s < LK_S_MAX; ++s) q[s] = (s < S) ? *reinterpret_cast<const float4*>(s_raw + (lane * S + s) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
             const LkRayOut o = lk_composite_vals(q, chas, cz, S, tl.coef, gd);
-            tl.depth[r] = o.depth; tl.var[r] = o.var;
-            tl.color[3 * r] = o.c0; tl.color[3 * r + 1] = o.c1; tl.color[3 * r + 2] = o.c2;
-            tl.valid_ray[r] = o.valid ? 1 : 0;
-            const bool present = gd > 0.0f;
-            tv = present ? fabsf(gd - o.depth) / sqrtf(o.var + 1e-10f) : 0.0f;
-            cv = present ? 1.0f : 0.0f;
-            tl.resid[r] = tl.median ? (present ? fabsf(gd - o.depth) : -1.0f) : tv;
+            lk_store_ray_out(tl, r, o);
+            const LkTrackResid pr = lk_track_resid(gd, o.depth, o.var, tl.median);
+            tv = pr.tv; cv = pr.cv;
+            tl.resid[r] = pr.resid;
         }
 #pragma unroll
         for (int o = 4; o > 0; o >>= 1) { tv += __shfl_xor(tv, o); cv += __shfl_xor(cv, o); }       // n_rays <= 8 (S >= 4)

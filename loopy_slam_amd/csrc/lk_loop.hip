@@ -31,18 +31,6 @@ int lk_launch_composite_loss_exposure(const LkCompositeArgs& ca, const float* gt
 
 #define LK_TRACK_FUSED_MAX_R LK_MASK_REG_MAX          // rays a single workgroup keeps in registers (8 per thread)
 
-// ------------------------------------------------------------------ helpers
-__device__ __forceinline__ float lp_block_sum_1024(float v, float* sh /*[16]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if (lk_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += sh[i];
-    return s;
-}
 // ------------------------------------------------------------------ k_pregather
 // Batch assembly of ALL iterations of a frame in one launch (workgroup b = iteration b): pixel gather (get_samples,
 // common.py:237-259), inside mask (Tracker.py:153-160 / Mapper.py:674-681: rejected rays become absent, gt_depth = 0) and - for
@@ -169,13 +157,10 @@ __global__ __launch_bounds__(256) void k_track_composite(LkTrackLossArgs a) {
     if (r < a.R) {
         const float gd = a.gt_depth[r];
         const LkRayOut o = lk_composite_ray(a.raw, a.z, a.nbr_count, r, a.S, a.min_nn, a.coef, gd);
-        a.depth[r] = o.depth; a.var[r] = o.var;
-        a.color[3 * r] = o.c0; a.color[3 * r + 1] = o.c1; a.color[3 * r + 2] = o.c2;
-        a.valid_ray[r] = o.valid ? 1 : 0;
-        const bool present = gd > 0.0f;                    // absent rays take no part in the mean (filtered before the render)
-        tv = present ? fabsf(gd - o.depth) / sqrtf(o.var + 1e-10f) : 0.0f;
-        cv = present ? 1.0f : 0.0f;
-        a.resid[r] = a.median ? (present ? fabsf(gd - o.depth) : -1.0f) : tv;
+        lk_store_ray_out(a, r, o);
+        const LkTrackResid q = lk_track_resid(gd, o.depth, o.var, a.median);
+        tv = q.tv; cv = q.cv;
+        a.resid[r] = q.resid;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { tv += __shfl_xor(tv, o); cv += __shfl_xor(cv, o); }

@@ -13,19 +13,7 @@
 #include <math.h>
 #include <string.h>
 
-// ------------------------------------------------------------------ block reduction helper
-__device__ __forceinline__ float block_sum_256(float v, float* sh /*[4]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if (lk_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-__device__ __forceinline__ float sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
-
-// ------------------------------------------------------------------ mapper loss
+// ------------------------------------------------------------------ mapper loss (per-ray terms: lk_loss_dev.h)
 __global__ __launch_bounds__(256) void k_loss_mapper(int R, const float* __restrict__ depth, const float* __restrict__ color,
                                                      const uint8_t* __restrict__ valid, const float* __restrict__ gt_depth,
                                                      const float* __restrict__ gt_color, float w_color, int use_color,
@@ -35,26 +23,14 @@ __global__ __launch_bounds__(256) void k_loss_mapper(int R, const float* __restr
     const int r = blockIdx.x * 256 + (int)threadIdx.x;
     float geo = 0.0f, col = 0.0f, cnt = 0.0f;
     if (r < R) {
-        const float d = depth[r], g = gt_depth[r];
-        const bool m = (g > 0.0f) && valid[r] && !(d != d);
-        float dd = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-        if (m) {
-            geo = fabsf(g - d);
-            dd = sgn(d - g);
-            cnt = 1.0f;
-            if (use_color) {
-                const float e0 = color[3 * r] - gt_color[3 * r], e1 = color[3 * r + 1] - gt_color[3 * r + 1],
-                            e2 = color[3 * r + 2] - gt_color[3 * r + 2];
-                col = fabsf(e0) + fabsf(e1) + fabsf(e2);
-                dc0 = w_color * sgn(e0); dc1 = w_color * sgn(e1); dc2 = w_color * sgn(e2);
-            }
-        }
-        d_depth[r] = dd;
-        d_color[3 * r] = dc0; d_color[3 * r + 1] = dc1; d_color[3 * r + 2] = dc2;
+        const LkMapRayLoss l = lk_map_ray_loss(gt_depth[r], depth[r], valid[r] != 0, color[3 * r], color[3 * r + 1], color[3 * r + 2], gt_color, r, w_color, use_color);
+        geo = l.geo; col = l.col; cnt = l.cnt;
+        d_depth[r] = l.dd;
+        d_color[3 * r] = l.dc0; d_color[3 * r + 1] = l.dc1; d_color[3 * r + 2] = l.dc2;
     }
-    geo = block_sum_256(geo, sh);
-    col = block_sum_256(col, sh);
-    cnt = block_sum_256(cnt, sh);
+    geo = lk_block_sum<4>(geo, sh);
+    col = lk_block_sum<4>(col, sh);
+    cnt = lk_block_sum<4>(cnt, sh);
     if (threadIdx.x == 0) {
         atomicAdd(out + 0, geo + (use_color ? w_color * col : 0.0f));
         atomicAdd(out + 1, geo);
@@ -64,28 +40,22 @@ __global__ __launch_bounds__(256) void k_loss_mapper(int R, const float* __restr
 }
 
 // ------------------------------------------------------------------ tracker loss (two passes: mean of the normalised residual)
-// MEDIAN (tracking.handle_dynamic: False, Tracker.py:177-179): scratch[r] = |gt - depth| (sign bit set for an absent ray), no sums;
-// k_loss_tracker_median then leaves 10 x the median in scratch[R] and pass 2 masks by it
+// pass 1 leaves lk_track_resid's resid of every ray in scratch[r] and adds the two terms of the mean to scratch[R], scratch[R + 1];
+// MEDIAN (tracking.handle_dynamic: False): no sums - k_loss_tracker_median then leaves 10 x the median in scratch[R] and pass 2 masks by it
 template <bool MEDIAN>
 __global__ __launch_bounds__(256) void k_loss_tracker_pass1(int R, const float* __restrict__ depth, const float* __restrict__ var,
                                                             const float* __restrict__ gt_depth, float* __restrict__ scratch) {
     __shared__ float sh[4];
     const int r = blockIdx.x * 256 + (int)threadIdx.x;
-    if (MEDIAN) {
-        if (r < R) scratch[r] = (gt_depth[r] > 0.0f) ? fabsf(gt_depth[r] - depth[r]) : -1.0f;
-        return;
-    }
-    // Rays with gt_depth <= 0 are "absent": the reference filters them out BEFORE rendering
-    // (get_samples depth_filter + inside mask, Tracker.py:142-160), so they take no part in the mean.
     float t = 0.0f, c = 0.0f;
     if (r < R) {
-        const bool present = gt_depth[r] > 0.0f;
-        t = present ? fabsf(gt_depth[r] - depth[r]) / sqrtf(var[r] + 1e-10f) : 0.0f;
-        c = present ? 1.0f : 0.0f;
-        scratch[r] = t;
+        const LkTrackResid q = lk_track_resid(gt_depth[r], depth[r], var[r], MEDIAN);
+        t = q.tv; c = q.cv;
+        scratch[r] = q.resid;
     }
-    t = block_sum_256(t, sh);
-    c = block_sum_256(c, sh);
+    if (MEDIAN) return;
+    t = lk_block_sum<4>(t, sh);
+    c = lk_block_sum<4>(c, sh);
     if (threadIdx.x == 0) { atomicAdd(scratch + R, t); atomicAdd(scratch + R + 1, c); }
 }
 
@@ -93,6 +63,16 @@ __global__ __launch_bounds__(1024) void k_loss_tracker_median(int R, float* __re
     __shared__ LkMedianShared S;
     const float thr = lk_block_median10(scratch, R, S);
     if (threadIdx.x == 0) scratch[R] = thr;
+}
+
+// what pass 2 reads of ray r; resid: pass 1's
+__device__ __forceinline__ LkTrackRayIn loss_tracker_ray_in(const float* __restrict__ depth, const float* __restrict__ var, const float* __restrict__ color,
+                                                            const float* __restrict__ gt_depth, const float* __restrict__ gt_color, float resid, int r) {
+    LkTrackRayIn i;
+    i.d = depth[r]; i.v = var[r]; i.g = gt_depth[r]; i.tm = resid;
+    i.c0 = color[3 * r]; i.c1 = color[3 * r + 1]; i.c2 = color[3 * r + 2];
+    i.g0 = gt_color[3 * r]; i.g1 = gt_color[3 * r + 1]; i.g2 = gt_color[3 * r + 2];
+    return i;
 }
 
 template <bool MEDIAN>
@@ -106,26 +86,14 @@ __global__ __launch_bounds__(256) void k_loss_tracker_pass2(int R, const float* 
     const float thr = MEDIAN ? scratch[R] : 10.0f * (scratch[R] / fmaxf(scratch[R + 1], 1.0f));
     float geo = 0.0f, col = 0.0f, cnt = 0.0f;
     if (r < R) {
-        const float d = depth[r], v = var[r], g = gt_depth[r];
-        const float t = MEDIAN ? fabsf(g - d) / sqrtf(v + 1e-10f) : scratch[r];     // the loss term stays uncertainty-normalised
-        const float tm = MEDIAN ? scratch[r] : t;                                   // what the mask compares
-        const bool m = (tm < thr) && (g > 0.0f) && !(d != d) && !(v != v);
-        float dd = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-        if (m) {
-            geo = fminf(fmaxf(t, 0.0f), 1e3f);
-            if (t <= 1e3f) dd = sgn(d - g) / sqrtf(v + 1e-10f);
-            cnt = 1.0f;
-            const float e0 = color[3 * r] - gt_color[3 * r], e1 = color[3 * r + 1] - gt_color[3 * r + 1],
-                        e2 = color[3 * r + 2] - gt_color[3 * r + 2];
-            col = fabsf(e0) + fabsf(e1) + fabsf(e2);
-            if (use_color) { dc0 = w_color * sgn(e0); dc1 = w_color * sgn(e1); dc2 = w_color * sgn(e2); }
-        }
-        d_depth[r] = dd;
-        d_color[3 * r] = dc0; d_color[3 * r + 1] = dc1; d_color[3 * r + 2] = dc2;
+        const LkTrackRayLoss l = lk_track_ray_loss(loss_tracker_ray_in(depth, var, color, gt_depth, gt_color, scratch[r], r), thr, MEDIAN, use_color, w_color);
+        geo = l.geo; col = l.col; cnt = l.cnt;
+        d_depth[r] = l.dd;
+        d_color[3 * r] = l.dc0; d_color[3 * r + 1] = l.dc1; d_color[3 * r + 2] = l.dc2;
     }
-    geo = block_sum_256(geo, sh);
-    col = block_sum_256(col, sh);
-    cnt = block_sum_256(cnt, sh);
+    geo = lk_block_sum<4>(geo, sh);
+    col = lk_block_sum<4>(col, sh);
+    cnt = lk_block_sum<4>(cnt, sh);
     if (threadIdx.x == 0) {
         atomicAdd(out + 0, geo + (use_color ? w_color * col : 0.0f));
         atomicAdd(out + 1, geo);
@@ -138,18 +106,6 @@ __global__ __launch_bounds__(256) void k_loss_tracker_pass2(int R, const float* 
 // R <= LK_LOSS_1WG_MAX rays: a single 1024-thread workgroup owns the whole batch, so the sums need neither atomics
 // nor a zero-fill launch, the tracker's two passes become one kernel, and the result is order-deterministic.
 #define LK_LOSS_1WG_MAX 16384
-__device__ __forceinline__ float block_sum_1024(float v, float* sh /*[16]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if (lk_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += sh[i];
-    return s;
-}
-
 __global__ __launch_bounds__(1024) void k_loss_mapper_1wg(int R, const float* __restrict__ depth, const float* __restrict__ color,
                                                           const uint8_t* __restrict__ valid, const float* __restrict__ gt_depth,
                                                           const float* __restrict__ gt_color, float w_color, int use_color,
@@ -158,26 +114,14 @@ __global__ __launch_bounds__(1024) void k_loss_mapper_1wg(int R, const float* __
     __shared__ float sh[16];
     float geo = 0.0f, col = 0.0f, cnt = 0.0f;
     for (int r = threadIdx.x; r < R; r += 1024) {
-        const float d = depth[r], g = gt_depth[r];
-        const bool m = (g > 0.0f) && valid[r] && !(d != d);
-        float dd = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-        if (m) {
-            geo += fabsf(g - d);
-            dd = sgn(d - g);
-            cnt += 1.0f;
-            if (use_color) {
-                const float e0 = color[3 * r] - gt_color[3 * r], e1 = color[3 * r + 1] - gt_color[3 * r + 1],
-                            e2 = color[3 * r + 2] - gt_color[3 * r + 2];
-                col += fabsf(e0) + fabsf(e1) + fabsf(e2);
-                dc0 = w_color * sgn(e0); dc1 = w_color * sgn(e1); dc2 = w_color * sgn(e2);
-            }
-        }
-        d_depth[r] = dd;
-        d_color[3 * r] = dc0; d_color[3 * r + 1] = dc1; d_color[3 * r + 2] = dc2;
+        const LkMapRayLoss l = lk_map_ray_loss(gt_depth[r], depth[r], valid[r] != 0, color[3 * r], color[3 * r + 1], color[3 * r + 2], gt_color, r, w_color, use_color);
+        geo += l.geo; col += l.col; cnt += l.cnt;
+        d_depth[r] = l.dd;
+        d_color[3 * r] = l.dc0; d_color[3 * r + 1] = l.dc1; d_color[3 * r + 2] = l.dc2;
     }
-    geo = block_sum_1024(geo, sh);
-    col = block_sum_1024(col, sh);
-    cnt = block_sum_1024(cnt, sh);
+    geo = lk_block_sum<16>(geo, sh);
+    col = lk_block_sum<16>(col, sh);
+    cnt = lk_block_sum<16>(cnt, sh);
     if (threadIdx.x == 0) {
         out[0] = geo + (use_color ? w_color * col : 0.0f);
         out[1] = geo; out[2] = col; out[3] = cnt;
@@ -194,18 +138,17 @@ __global__ __launch_bounds__(1024) void k_loss_tracker_1wg(int R, const float* _
     __shared__ float sh[16];
     __shared__ LkMedianShared S;
     constexpr int VPT = LK_LOSS_1WG_MAX / 1024;
-    float tv[VPT], tm[VPT];
+    float tm[VPT];
     float tsum = 0.0f, csum = 0.0f;
 #pragma unroll
     for (int q = 0; q < VPT; ++q) {
         const int r = (int)threadIdx.x + 1024 * q;
-        tv[q] = 0.0f; tm[q] = 0.0f;
+        tm[q] = 0.0f;
         if (r < R) {
-            const bool present = gt_depth[r] > 0.0f;     // absent rays take no part in the mean (see pass1 above)
-            tv[q] = present ? fabsf(gt_depth[r] - depth[r]) / sqrtf(var[r] + 1e-10f) : 0.0f;
-            tsum += tv[q];
-            csum += present ? 1.0f : 0.0f;
-            if (MEDIAN) { tm[q] = present ? fabsf(gt_depth[r] - depth[r]) : -1.0f; scratch[r] = tm[q]; }
+            const LkTrackResid p = lk_track_resid(gt_depth[r], depth[r], var[r], MEDIAN);
+            tsum += p.tv; csum += p.cv;
+            tm[q] = p.resid;
+            if (MEDIAN) scratch[r] = tm[q];
         }
     }
     float thr;
@@ -213,8 +156,8 @@ __global__ __launch_bounds__(1024) void k_loss_tracker_1wg(int R, const float* _
         __syncthreads();                                   // the workgroup's own stores to scratch
         thr = lk_block_median10(scratch, R, S);
     } else {
-        tsum = block_sum_1024(tsum, sh);
-        csum = block_sum_1024(csum, sh);
+        tsum = lk_block_sum<16>(tsum, sh);
+        csum = lk_block_sum<16>(csum, sh);
         thr = 10.0f * (tsum / fmaxf(csum, 1.0f));
     }
     float geo = 0.0f, col = 0.0f, cnt = 0.0f;
@@ -222,25 +165,15 @@ __global__ __launch_bounds__(1024) void k_loss_tracker_1wg(int R, const float* _
     for (int q = 0; q < VPT; ++q) {
         const int r = (int)threadIdx.x + 1024 * q;
         if (r < R) {
-            const float d = depth[r], v = var[r], g = gt_depth[r], t = tv[q];
-            const bool m = ((MEDIAN ? tm[q] : t) < thr) && (g > 0.0f) && !(d != d) && !(v != v);
-            float dd = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-            if (m) {
-                geo += fminf(fmaxf(t, 0.0f), 1e3f);
-                if (t <= 1e3f) dd = sgn(d - g) / sqrtf(v + 1e-10f);
-                cnt += 1.0f;
-                const float e0 = color[3 * r] - gt_color[3 * r], e1 = color[3 * r + 1] - gt_color[3 * r + 1],
-                            e2 = color[3 * r + 2] - gt_color[3 * r + 2];
-                col += fabsf(e0) + fabsf(e1) + fabsf(e2);
-                if (use_color) { dc0 = w_color * sgn(e0); dc1 = w_color * sgn(e1); dc2 = w_color * sgn(e2); }
-            }
-            d_depth[r] = dd;
-            d_color[3 * r] = dc0; d_color[3 * r + 1] = dc1; d_color[3 * r + 2] = dc2;
+            const LkTrackRayLoss l = lk_track_ray_loss(loss_tracker_ray_in(depth, var, color, gt_depth, gt_color, tm[q], r), thr, MEDIAN, use_color, w_color);
+            geo += l.geo; col += l.col; cnt += l.cnt;
+            d_depth[r] = l.dd;
+            d_color[3 * r] = l.dc0; d_color[3 * r + 1] = l.dc1; d_color[3 * r + 2] = l.dc2;
         }
     }
-    geo = block_sum_1024(geo, sh);
-    col = block_sum_1024(col, sh);
-    cnt = block_sum_1024(cnt, sh);
+    geo = lk_block_sum<16>(geo, sh);
+    col = lk_block_sum<16>(col, sh);
+    cnt = lk_block_sum<16>(cnt, sh);
     if (threadIdx.x == 0) {
         out[0] = geo + (use_color ? w_color * col : 0.0f);
         out[1] = geo; out[2] = col; out[3] = cnt;
@@ -265,21 +198,13 @@ __global__ __launch_bounds__(256) void k_adam_x(AdamArgs a, ExposureStepArgs xa)
 }
 
 // ------------------------------------------------------------------ pose -> rays
-__device__ __forceinline__ void quat_rot(const float* __restrict__ cam, float (&Rm)[9]) {
-    const float qr = cam[0], qi = cam[1], qj = cam[2], qk = cam[3];
-    const float s = 2.0f / (qr * qr + qi * qi + qj * qj + qk * qk);
-    Rm[0] = 1.0f - s * (qj * qj + qk * qk); Rm[1] = s * (qi * qj - qk * qr); Rm[2] = s * (qi * qk + qj * qr);
-    Rm[3] = s * (qi * qj + qk * qr); Rm[4] = 1.0f - s * (qi * qi + qk * qk); Rm[5] = s * (qj * qk - qi * qr);
-    Rm[6] = s * (qi * qk - qj * qr); Rm[7] = s * (qj * qk + qi * qr); Rm[8] = 1.0f - s * (qi * qi + qj * qj);
-}
-
 __global__ __launch_bounds__(256) void k_rays_from_pose(const float* __restrict__ cam, const float* __restrict__ pi,
                                                         const float* __restrict__ pj, int R, float fx, float fy, float cx,
                                                         float cy, float* __restrict__ ro, float* __restrict__ rd) {
     const int r = blockIdx.x * 256 + (int)threadIdx.x;
     if (r >= R) return;
     float Rm[9];
-    quat_rot(cam, Rm);
+    lk_quat_rot(cam, Rm);
     const float d0 = (pi[r] - cx) / fx, d1 = -(pj[r] - cy) / fy, d2 = -1.0f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -306,30 +231,15 @@ __global__ __launch_bounds__(256) void k_pose_bwd(const float* __restrict__ cam,
         }
     }
 #pragma unroll
-    for (int q = 0; q < 9; ++q) { const float s = block_sum_256(G[q], sh); if (threadIdx.x == 0) acc[q] = s; }
+    for (int q = 0; q < 9; ++q) { const float s = lk_block_sum<4>(G[q], sh); if (threadIdx.x == 0) acc[q] = s; }
 #pragma unroll
-    for (int q = 0; q < 3; ++q) { const float s = block_sum_256(gT[q], sh); if (threadIdx.x == 0) acc[9 + q] = s; }
+    for (int q = 0; q < 3; ++q) { const float s = lk_block_sum<4>(gT[q], sh); if (threadIdx.x == 0) acc[9 + q] = s; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float qr = cam[0], qi = cam[1], qj = cam[2], qk = cam[3];
-        const float N = qr * qr + qi * qi + qj * qj + qk * qk, s = 2.0f / N;
-        const float P[9] = {-(qj * qj + qk * qk), qi * qj - qk * qr, qi * qk + qj * qr,
-                            qi * qj + qk * qr, -(qi * qi + qk * qk), qj * qk - qi * qr,
-                            qi * qk - qj * qr, qj * qk + qi * qr, -(qi * qi + qj * qj)};
-        float gp = 0.0f;
+        float gc[7];
+        lk_pose_grad(cam, acc, gc);
 #pragma unroll
-        for (int q = 0; q < 9; ++q) gp += acc[q] * P[q];
-        const float* g = acc;
-        const float dPr = g[1] * (-qk) + g[2] * qj + g[3] * qk + g[5] * (-qi) + g[6] * (-qj) + g[7] * qi;
-        const float dPi = g[1] * qj + g[2] * qk + g[3] * qj + g[4] * (-2.0f * qi) + g[5] * (-qr) + g[6] * qk + g[7] * qr + g[8] * (-2.0f * qi);
-        const float dPj = g[0] * (-2.0f * qj) + g[1] * qi + g[2] * qr + g[3] * qi + g[5] * qk + g[6] * (-qr) + g[7] * qk + g[8] * (-2.0f * qj);
-        const float dPk = g[0] * (-2.0f * qk) + g[1] * (-qr) + g[2] * qi + g[3] * qr + g[4] * (-2.0f * qk) + g[5] * qj + g[6] * qi + g[7] * qj;
-        const float ds = -s * s;            // d s / d q_x = -s^2 q_x
-        g_cam[0] = ds * qr * gp + s * dPr;
-        g_cam[1] = ds * qi * gp + s * dPi;
-        g_cam[2] = ds * qj * gp + s * dPj;
-        g_cam[3] = ds * qk * gp + s * dPk;
-        g_cam[4] = acc[9]; g_cam[5] = acc[10]; g_cam[6] = acc[11];
+        for (int e = 0; e < 7; ++e) g_cam[e] = gc[e];
     }
 }
 
@@ -490,7 +400,7 @@ __global__ __launch_bounds__(256) void k_exposure_bwd(const float* __restrict__ 
 
 // Mapper loss of the colour stage with exposure encoding (Mapper.py:691-720): the rays of keyframe f get
 // sigmoid(logits @ rot_f + trans_f); returns d depth, d logits, [loss, geo, colour, #masked] and d loss / d affine [F,12].
-// COMP (the mapping loop): the composite of the ray (k_composite's arithmetic and outputs) in the same thread - one launch instead of two.
+// COMP (the mapping loop): the composite of the ray (lk_composite_ray, k_composite's outputs) in the same thread - one launch instead of two.
 // d affine: the rays of a batch are grouped by keyframe, so the lanes of a wave share one or two keyframes - the twelve terms are summed over
 // the lanes of a keyframe by shuffles and added to the workgroup's LDS table once per wave and keyframe (one LDS float atomic per LANE and
 // term retired a lane every two cycles with all 64 on the same address: most of the kernel's 14 us).
@@ -516,9 +426,7 @@ __global__ __launch_bounds__(256) void k_loss_mapper_exposure(LkCompositeArgs ca
             gd = gt_depth[r];
             if (COMP) {
                 const LkRayOut ro = lk_composite_ray(ca.raw, ca.z, ca.nbr_count, r, ca.S, ca.min_nn, ca.coef, ca.keep_depth ? 1.0f : gd);
-                ca.depth[r] = ro.depth; ca.var[r] = ro.var;
-                ca.color[3 * r] = ro.c0; ca.color[3 * r + 1] = ro.c1; ca.color[3 * r + 2] = ro.c2;
-                ca.valid_ray[r] = ro.valid ? 1 : 0;
+                lk_store_ray_out(ca, r, ro);
                 d = ro.depth; l0 = ro.c0; l1 = ro.c1; l2 = ro.c2; val = ro.valid;
             } else {
                 d = depth[r]; val = valid[r] != 0;
@@ -539,10 +447,10 @@ __global__ __launch_bounds__(256) void k_loss_mapper_exposure(LkCompositeArgs ca
                 const float y = lk_sigmoid(pre);
                 const float e = y - gt_color[3 * r + c];
                 col += fabsf(e);
-                dp[c] = w_color * sgn(e) * y * (1.0f - y);
+                dp[c] = w_color * lk_sgn(e) * y * (1.0f - y);
             }
             geo += fabsf(gd - d);
-            dd = sgn(d - gd);
+            dd = lk_sgn(d - gd);
             cnt += 1.0f;
             const float lv[3] = {l0, l1, l2};
 #pragma unroll

@@ -92,7 +92,7 @@ __device__ __forceinline__ void sample_interp_block(const LkSampleArgs& a, int b
     float o3[3], d3[3];
     if (POSE) {
         float Rm[9];
-        lp_quat_rot(s_cam, Rm);
+        lk_quat_rot(s_cam, Rm);
         const float d0 = (early->pix_i - f->cx) / f->fx, d1 = -(early->pix_j - f->cy) / f->fy, d2 = -1.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -269,30 +269,13 @@ __global__ __launch_bounds__(256) void k_composite(LkCompositeArgs a) {
     if (r < a.R) {
         const float gd = a.gt_depth[r];
         const LkRayOut ro = lk_composite_ray(a.raw, a.z, a.nbr_count, r, a.S, a.min_nn, a.coef, a.keep_depth ? 1.0f : gd);
-        const float dout = ro.depth, o0 = ro.c0, o1 = ro.c1, o2 = ro.c2;
-        const bool valid = ro.valid;
-        a.depth[r] = dout;
-        a.var[r] = ro.var;
-        a.color[3 * r] = o0; a.color[3 * r + 1] = o1; a.color[3 * r + 2] = o2;
-        a.valid_ray[r] = valid ? 1 : 0;
+        lk_store_ray_out(a, r, ro);
         if (a.loss_out) {
-            const bool m = (gd > 0.0f) && valid && !(dout != dout);
-            float dd = 0.0f, d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
-            if (m) {
-                l_geo = fabsf(gd - dout);
-                dd = (dout > gd) ? 1.0f : ((dout < gd) ? -1.0f : 0.0f);
-                l_cnt = 1.0f;
-                if (a.use_color) {
-                    const float e0 = o0 - a.gt_color[3 * r], e1 = o1 - a.gt_color[3 * r + 1], e2 = o2 - a.gt_color[3 * r + 2];
-                    l_col = fabsf(e0) + fabsf(e1) + fabsf(e2);
-                    d0 = a.w_color * ((e0 > 0.0f) ? 1.0f : ((e0 < 0.0f) ? -1.0f : 0.0f));
-                    d1 = a.w_color * ((e1 > 0.0f) ? 1.0f : ((e1 < 0.0f) ? -1.0f : 0.0f));
-                    d2 = a.w_color * ((e2 > 0.0f) ? 1.0f : ((e2 < 0.0f) ? -1.0f : 0.0f));
-                }
-            }
-            a.d_depth[r] = dd;
-            a.d_color[3 * r] = d0; a.d_color[3 * r + 1] = d1; a.d_color[3 * r + 2] = d2;
-            if (a.d_raw) lk_composite_bwd_ray(a.raw, a.z, a.nbr_count, r, a.S, a.min_nn, a.coef, gd, dd, 0.0f, d0, d1, d2, a.d_raw);
+            const LkMapRayLoss l = lk_map_ray_loss(gd, ro.depth, ro.valid, ro.c0, ro.c1, ro.c2, a.gt_color, r, a.w_color, a.use_color);
+            l_geo = l.geo; l_col = l.col; l_cnt = l.cnt;
+            a.d_depth[r] = l.dd;
+            a.d_color[3 * r] = l.dc0; a.d_color[3 * r + 1] = l.dc1; a.d_color[3 * r + 2] = l.dc2;
+            if (a.d_raw) lk_composite_bwd_ray(a.raw, a.z, a.nbr_count, r, a.S, a.min_nn, a.coef, gd, l.dd, 0.0f, l.dc0, l.dc1, l.dc2, a.d_raw);
         }
     }
     if (a.loss_out) {

@@ -1,11 +1,9 @@
-// Device code of the tracking loop's pose step (lk_loop.hip): quaternion -> rotation, gradient from the ray moments, Adam,
-// rays of the next batch.
+// Device code of the tracking loop (lk_loop.hip): the loss prologue of its k_decode_bwd, and the pose step - gradient from the ray
+// moments, Adam, rays of the next batch.  (The loss and pose formulas themselves: lk_loss_dev.h.)
 #pragma once
 #include "lk_common.h"
 #include "lk_kernels.h"
 #include "lk_composite_dev.h"
-
-__device__ __forceinline__ float lp_sgn(float x) { return (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : 0.0f); }
 
 // ---- the tracker's loss (Tracker.py:169-191) per ray, in the prologue of the tracking loop's k_decode_bwd
 // mask threshold 10 x the batch mean of the normalised residuals from pass 1's block sums: a whole wave calls, every wave of every workgroup
@@ -37,30 +35,12 @@ __device__ __forceinline__ float lk_track_threshold(const LkTrackLossArgs& a, in
     for (int o = 32; o > 0; o >>= 1) { ts += __shfl_xor(ts, o); cs += __shfl_xor(cs, o); }
     return 10.0f * (ts / fmaxf(cs, 1.0f));
 }
-struct LkTrackRayLoss { float dd, dc0, dc1, dc2, geo, col, cnt, gt; };
-struct LkTrackRayIn { float d, v, g, tm, c0, c1, c2, g0, g1, g2; };
 __device__ __forceinline__ LkTrackRayIn lk_track_ray_in(const LkTrackLossArgs& a, int r) {
     LkTrackRayIn i;
     i.d = a.depth[r]; i.v = a.var[r]; i.g = a.gt_depth[r]; i.tm = a.resid[r];
     i.c0 = a.color[3 * r]; i.c1 = a.color[3 * r + 1]; i.c2 = a.color[3 * r + 2];
     i.g0 = a.gt_color[3 * r]; i.g1 = a.gt_color[3 * r + 1]; i.g2 = a.gt_color[3 * r + 2];
     return i;
-}
-__device__ __forceinline__ LkTrackRayLoss lk_track_ray_loss(const LkTrackLossArgs& a, const LkTrackRayIn& in, float thr) {
-    LkTrackRayLoss o;
-    const float d = in.d, v = in.v, g = in.g, tm = in.tm;
-    const float tt = a.median ? fabsf(g - d) / sqrtf(v + 1e-10f) : tm;          // the loss term stays uncertainty-normalised
-    const bool m = (tm < thr) && (g > 0.0f) && !(d != d) && !(v != v);
-    o.dd = 0.0f; o.dc0 = 0.0f; o.dc1 = 0.0f; o.dc2 = 0.0f; o.geo = 0.0f; o.col = 0.0f; o.cnt = 0.0f; o.gt = g;
-    if (m) {
-        o.geo = fminf(fmaxf(tt, 0.0f), 1e3f);
-        if (tt <= 1e3f) o.dd = lp_sgn(d - g) / sqrtf(v + 1e-10f);
-        o.cnt = 1.0f;
-        const float e0 = in.c0 - in.g0, e1 = in.c1 - in.g1, e2 = in.c2 - in.g2;
-        o.col = fabsf(e0) + fabsf(e1) + fabsf(e2);
-        if (a.use_color) { o.dc0 = a.w_color * lp_sgn(e0); o.dc1 = a.w_color * lp_sgn(e1); o.dc2 = a.w_color * lp_sgn(e2); }
-    }
-    return o;
 }
 // d raw of sample sp (its lane calls; all 64 lanes of the wave must call - the threshold is a wave sum); *row: the ray's loss terms
 __device__ __forceinline__ float4 lk_track_draw(const LkTrackLossArgs& a, int n_part, int sp, LkTrackRayLoss* row) {
@@ -71,28 +51,16 @@ __device__ __forceinline__ float4 lk_track_draw(const LkTrackLossArgs& a, int n_
     LkRayState st;
     lk_ray_state(a.raw, a.z, a.nbr_count, r, a.S, a.min_nn, a.coef, st);
     const float thr = lk_track_threshold(a, n_part, parts);
-    const LkTrackRayLoss o = lk_track_ray_loss(a, in, thr);
+    const LkTrackRayLoss o = lk_track_ray_loss(in, thr, a.median, a.use_color, a.w_color);
     if (row) *row = o;
     float4 out[LK_S_MAX];
     lk_ray_grad(st, a.S, a.coef, o.gt, o.dd, 0.0f, o.dc0, o.dc1, o.dc2, out);
     const int s_own = sp - r * a.S;
-    float4 res = out[0];
-#pragma unroll
-    for (int s = 1; s < LK_S_MAX; ++s)
-        if (s == s_own) res = out[s];
+    LK_PICK_SAMPLE(res, out, s_own)
     return res;
 }
 
-__device__ __forceinline__ void lp_quat_rot(const float* __restrict__ cam, float (&Rm)[9]) {       // common.py:301-324
-    const float qr = cam[0], qi = cam[1], qj = cam[2], qk = cam[3];
-    const float s = 2.0f / (qr * qr + qi * qi + qj * qj + qk * qk);
-    Rm[0] = 1.0f - s * (qj * qj + qk * qk); Rm[1] = s * (qi * qj - qk * qr); Rm[2] = s * (qi * qk + qj * qr);
-    Rm[3] = s * (qi * qj + qk * qr); Rm[4] = 1.0f - s * (qi * qi + qk * qk); Rm[5] = s * (qj * qk - qi * qr);
-    Rm[6] = s * (qi * qk - qj * qr); Rm[7] = s * (qj * qk + qi * qr); Rm[8] = 1.0f - s * (qi * qi + qj * qj);
-}
-
-
-// pose gradient from the ray moments (k_pose_bwd's formulas), Adam on (T | q) (Tracker.py:317-352), the candidate pose log - by a whole
+// pose gradient from the ray moments (lk_pose_grad), Adam on (T | q) (Tracker.py:317-352), the candidate pose log - by a whole
 // workgroup of NW waves (all of its threads call); the stepped pose (do_update = 0: the pose as it is) is left in s_cam[7] (LDS) behind a barrier.
 // write: store the pose, its moments, the gradient and the log row (exactly one workgroup of a launch does).
 template <int NW>
@@ -142,23 +110,8 @@ __device__ __forceinline__ void lk_track_pose_step(const LkTrackFinalArgs& a, fl
         }
         __syncthreads();
         if (t == 0) {
-            const float qr = cam0[0], qi = cam0[1], qj = cam0[2], qk = cam0[3];
-            const float N = qr * qr + qi * qi + qj * qj + qk * qk, s = 2.0f / N;
-            const float P[9] = {-(qj * qj + qk * qk), qi * qj - qk * qr, qi * qk + qj * qr,
-                                qi * qj + qk * qr, -(qi * qi + qk * qk), qj * qk - qi * qr,
-                                qi * qk - qj * qr, qj * qk + qi * qr, -(qi * qi + qj * qj)};
-            float gp = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 9; ++q) gp += acc[q] * P[q];
-            const float* g = acc;
-            const float dPr = g[1] * (-qk) + g[2] * qj + g[3] * qk + g[5] * (-qi) + g[6] * (-qj) + g[7] * qi;
-            const float dPi = g[1] * qj + g[2] * qk + g[3] * qj + g[4] * (-2.0f * qi) + g[5] * (-qr) + g[6] * qk + g[7] * qr + g[8] * (-2.0f * qi);
-            const float dPj = g[0] * (-2.0f * qj) + g[1] * qi + g[2] * qr + g[3] * qi + g[5] * qk + g[6] * (-qr) + g[7] * qk + g[8] * (-2.0f * qj);
-            const float dPk = g[0] * (-2.0f * qk) + g[1] * (-qr) + g[2] * qi + g[3] * qr + g[4] * (-2.0f * qk) + g[5] * qj + g[6] * qi + g[7] * qj;
-            const float ds = -s * s;
             float gc[7];
-            gc[0] = ds * qr * gp + s * dPr; gc[1] = ds * qi * gp + s * dPi; gc[2] = ds * qj * gp + s * dPj; gc[3] = ds * qk * gp + s * dPk;
-            gc[4] = acc[9]; gc[5] = acc[10]; gc[6] = acc[11];
+            lk_pose_grad(cam0, acc, gc);
 #pragma unroll
             for (int e = 0; e < 7; ++e) {        // torch.optim.Adam, group T: elements 4..6, group q: 0..3 (as k_adam)
                 if (write && a.hist_pre) a.hist_pre[e] = cam0[e];
@@ -199,7 +152,7 @@ __device__ __forceinline__ void lk_track_final_body(const LkTrackFinalArgs& a) {
     lk_track_pose_step<NW>(a, s_cam, true);
     if (!a.rays_o) return;
     float Rm[9];
-    lp_quat_rot(s_cam, Rm);
+    lk_quat_rot(s_cam, Rm);
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
         const int r = t + 64 * NW * q;
