@@ -2,7 +2,8 @@
 //   k_interp_bwd    tracker mode: gradient through the interpolation weights to the sample position (decoder.py:191-229)
 //   k_seg_* / k_feat_gather  d c_geo / d c_col / per-neighbour rows -> feature-row gradients (rows sorted by point, one atomic per run)
 //   k_rays_bwd      d p -> d rays_o, d rays_d
-//   k_relpos_bwd    backward of the relative-position neighbour MLP (decoder.py:477-488)
+//   k_relpos_bwd    backward of the relative-position neighbour MLP (decoder.py:477-488); the wave tile it shares with the forward and the
+//                   fused variant (row set-up, input tiles, hidden layer, embedding derivative, w_sum / Hbar stores, tail): lk_relpos_dev.h
 //   k_relpos_bwd_fused / k_dw2_hbar   mapper mode: the same backward with linear1's / linear2's weight gradients inside
 //   k_wgrad(+_reduce)  colour-trunk weight gradients as streamed MFMA reductions over the sample rows
 //   k_bwd_reduce    every partial-sum reduction of a mapper 'color' backward + the fc_c products (fc_post_body) in one launch
@@ -10,6 +11,7 @@
 #include "lk_kernels.h"
 #include "lk_adam_dev.h"
 #include "lk_exposure_dev.h"
+#include "lk_relpos_dev.h"
 
 using namespace lkw;
 
@@ -389,12 +391,6 @@ __global__ __launch_bounds__(256) void k_rays_bwd(LkRaysBwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float rp_embed_unit(const float* __restrict__ B, int u, float a0, float a1, float a2) {
-    const int xi = (u < 10) ? u : u - 10;
-    const float x = lk_fourier_arg(a0, a1, a2, B[xi], B[10 + xi], B[20 + xi]);
-    return (u < 10) ? lk_sinf(x) : lk_cosf(x);
-}
-
 // H16 (the tracking loop's launch, k_relpos_interp_bwd: unit-scale colour loss gradients, no weight gradients): the two backward products on
 // fp16 pieces of the 2^10-scaled chain instead of bf16 pieces, as decode_bwd_col_wg<true> and the mapper's fused variant below - d c_col is
 // what the colour trunk's scaled chain delivered, so the same pre-scale puts d out, d hid in fp16's normal range; half the matrix
@@ -405,66 +401,18 @@ __device__ __forceinline__ void relpos_bwd_wave(const LkRelposBwdArgs& a, int sa
     typedef typename PC::T Piece;
     constexpr float SC = H16 ? 1024.0f : 1.0f, ISC = H16 ? 1.0f / 1024.0f : 1.0f;
     const int lane = lk_lane();
-    const int h = lane >> 5;
-    const int j = lane & 31;
-    const int sample = sample0 + (j >> 3);
-    const bool live = sample < a.P;
-    const int sp = live ? sample : a.P - 1;
-    const int nb_i = j & 7;
-    const int r = sp / a.S;
-    const float z = a.z[sp];
-    const float px = lk_madd_rn(a.rays_o[3 * r], a.rays_d[3 * r], z);
-    const float py = lk_madd_rn(a.rays_o[3 * r + 1], a.rays_d[3 * r + 1], z);
-    const float pz = lk_madd_rn(a.rays_o[3 * r + 2], a.rays_d[3 * r + 2], z);
-    int idx = a.nbr_idx[(size_t)sp * LK_K + nb_i];
-    const bool has = a.nbr_count[sp] >= a.min_nn;
-    float wgt = (idx >= 0 && has && live) ? a.nbr_w[(size_t)sp * LK_K + nb_i] : 0.0f;
-    if (idx < 0) idx = 0;
-    const float a0 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx], px));
-    const float a1 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 1], py));
-    const float a2 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 2], pz));
+    RP_ROW_SETUP(a, sample0, a.P, lane, true)
     const float* __restrict__ W = a.W;
     const u32x4* __restrict__ FB = reinterpret_cast<const u32x4*>(a.Wfrag);
     const u32x4* __restrict__ FP = FB + (H16 ? FRAGB_U4 : 0);      // the backward products' pieces
-    const size_t frow = (size_t)idx * LK_C;
-    constexpr bool f16 = F16;
     const bool want_w = !H16 && (a.flags & LK_FLAG_GRAD_WEIGHTS) != 0;
     const bool want_p = (a.flags & LK_FLAG_GRAD_RAYS) != 0;
     // ---- recompute the forward of this tile
-    f32x16 x0, x1;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int u0 = 8 * g + 4 * h;
-        if (u0 < ER) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x0[4 * g + t] = rp_embed_unit(W + R_EB, u0 + t, a0, a1, a2);
-        } else {
-            const float4 v = lk_feat4(a.col_feats, f16, frow + (u0 - ER));
-            x0[4 * g] = v.x; x0[4 * g + 1] = v.y; x0[4 * g + 2] = v.z; x0[4 * g + 3] = v.w;
-        }
-    }
-    x1 = lk_zero16();
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int u0 = 32 + 8 * g + 4 * h;
-        if (u0 < KR) {
-            const float4 v = lk_feat4(a.col_feats, f16, frow + (u0 - ER));
-            x1[4 * g] = v.x; x1[4 * g + 1] = v.y; x1[4 * g + 2] = v.z; x1[4 * g + 3] = v.w;
-        }
-    }
+    RP_INPUT_TILES(x0, x1, W, a.col_feats, F16, false)
     LK_STAMPW(1);                                    // (probe build) lists, positions, feature rows arrived; embedding evaluated
-    f32x16 hid[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) hid[nb] = lk_rowvec_tile(W + R_B1, nb * 32, lane);      // accumulators start from the bias
     // the recomputed forward uses the forward kernels' fp16x3 products (operands of O(1): embedding, features, activations)
     const u32x4* __restrict__ FH = FB + FRAGB_U4;
-    lk_gemm_h3<4, 2>(hid, FH + FM20_FWDH, 4, 0, 0, x0, 0, lane);
-    lk_gemm_h3<4, 2>(hid, FH + FM20_FWDH, 4, 2, 0, x1, 0, lane);       // units 32..55; registers 12..15 of x1 are zero
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) hid[nb][q] = lk_softplus100(hid[nb][q]);
-    }
+    RP_HIDDEN(hid, W, FH, x0, x1, lane)
     LK_STAMP(2);                                     // hidden layer recomputed
     // ---- d out = w * dc ; (tracker) d w = dc . out
     f32x16 dout[1];
@@ -494,13 +442,8 @@ __device__ __forceinline__ void relpos_bwd_wave(const LkRelposBwdArgs& a, int sa
     // has landed.  Every product's fragments are therefore fetched BEFORE the stores that precede it in the data flow
     // (one block ahead, pinned with scheduling barriers), and the big row stores go last.
     // ---- operands of the streamed weight-gradient reductions that need hid itself
-    //   linear2: dW2 = sum_rows (w d c) hid^T = sum_samples d c (sum_j w_j hid_j)^T  -> only the per-SAMPLE weighted
-    //            hidden vector Hbar [P][128] and the per-sample weight sum are needed (8x fewer rows, no hid rows)
-    if (want_w) {
-        float wsum = wgt;
-        wsum = lk_sum8<true>(wsum);
-        if (live && h == 0 && nb_i == 0) a.w_sum[sp] = wsum;
-    }
+    //   linear2 is reduced per SAMPLE: the weight sum here, the weighted hidden vector block by block below (RP_STORE_WSUM / RP_STORE_HBAR)
+    if (want_w) RP_STORE_WSUM(a)
     // ---- d hid = (W2^T d out) * softplus'(hid), block by block IN PLACE of hid (64 fewer live registers)
     f32x16 (&dhid)[4] = hid;
     const Piece db0 = PC::split(dout[0], 0), db1 = PC::split(dout[0], 1);
@@ -519,20 +462,7 @@ __device__ __forceinline__ void relpos_bwd_wave(const LkRelposBwdArgs& a, int sa
             for (int q = 0; q < 4; ++q) fx[q] = PC::load(FP + PC::tr(20), 2, q >> 1, q & 1, lane);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (want_w) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float v[4];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    float sred = wgt * hid[nb][4 * g + tt];
-                    sred = lk_sum8<true>(sred);
-                    v[tt] = sred;
-                }
-                if (live && nb_i == 0)
-                    *reinterpret_cast<float4*>(a.hbar + (size_t)sp * 128 + nb * 32 + 8 * g + 4 * h) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
+        if (want_w) { RP_STORE_HBAR(a, hid, nb) }
 #pragma unroll
         for (int q = 0; q < 16; ++q) dhid[nb][q] = t[q] * lk_softplus100_grad_from_out(hid[nb][q]);
     }
@@ -577,51 +507,9 @@ __device__ __forceinline__ void relpos_bwd_wave(const LkRelposBwdArgs& a, int sa
         }
     }
     float dax = 0.0f, day = 0.0f, daz = 0.0f;        // d loss / d (x_I - p), this lane's share
-    const float* B = W + R_EB;
-    // d sin = cos, d cos = -sin: the derivative of embedding unit u is (+/-) the FORWARD value of its partner unit u +/- 10,
-    // which x0 already holds - in this lane for 12 of the 20 units, in the lane of the other half-wave for units
-    // 2, 3, 6, 7 / 12, 13, 16, 17 (four exchanges) - instead of twelve more sin / cos evaluations per lane.
-    float fder[12];
-    {
-        const float r0 = __shfl_xor(h ? x0[4] : x0[8], 32), r1 = __shfl_xor(h ? x0[5] : x0[9], 32);
-        const float r2 = __shfl_xor(x0[2], 32), r3 = __shfl_xor(x0[3], 32);
-        fder[0] = x0[6]; fder[1] = x0[7]; fder[2] = r0; fder[3] = r1;                                        // units 0-3 | 4-7
-        fder[4] = h ? -r2 : x0[10]; fder[5] = h ? -r3 : x0[11]; fder[6] = -x0[0]; fder[7] = -x0[1];          // units 8-11 | 12-15
-        fder[8] = -r2; fder[9] = -r3; fder[10] = -x0[4]; fder[11] = -x0[5];                                  // units 16-19 (low half)
-    }
-#pragma unroll
-    for (int tile = 0; tile < 2; ++tile)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int u0 = 32 * tile + 8 * g + 4 * h;
-            const bool is_emb = u0 < ER;                 // uniform per half-wave (group 2 of tile 0 is mixed)
-            if (tile == 0 && g < 3) {                    // groups that hold embedding units in at least one half
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int u = u0 + t;
-                    const int xi = is_emb ? ((u < 10) ? u : u - 10) : 0;
-                    const float b0 = B[xi], b1 = B[10 + xi], b2 = B[20 + xi];
-                    float gx = 0.0f;
-                    if (is_emb) gx = dx[tile][4 * g + t] * fder[4 * g + t];
-                    if (want_p) {
-                        dax = fmaf(gx * LK_TWO_PI, b0, dax); day = fmaf(gx * LK_TWO_PI, b1, day); daz = fmaf(gx * LK_TWO_PI, b2, daz);
-                    }
-                    if (want_w) {                        // every lane takes part in the reductions (convergent shuffles)
-                        const float s0 = lk_half_wave_sum(gx * a0), s1 = lk_half_wave_sum(gx * a1), s2 = lk_half_wave_sum(gx * a2);
-                        if ((lane & 31) == LK_HWS_LANE && is_emb) {   // two units (sin, cos) and both half-waves meet in one slot: LDS atomics
-                            atomicAdd(part + xi, s0);
-                            atomicAdd(part + 10 + xi, s1);
-                            atomicAdd(part + 20 + xi, s2);
-                        }
-                    }
-                }
-            }
-            if (!is_emb && u0 < KR) {     // d feature row of this neighbour: summed per point by k_feat_gather
-                if ((a.flags & LK_FLAG_GRAD_FEATS) && live)
-                    *reinterpret_cast<float4*>(a.dfeat + ((size_t)sp * 8 + nb_i) * LK_C + (u0 - ER)) =
-                        make_float4(dx[tile][4 * g], dx[tile][4 * g + 1], dx[tile][4 * g + 2], dx[tile][4 * g + 3]);
-            }
-        }
+    // ---- d B (Fourier matrix), the d feature rows, d (x_I - p); with H16, d x is scaled back already
+    const RpFder fder = rp_fder(x0, h);
+    RP_TAIL(a, dx, fder, false, true, want_p, want_w, part, dax, day, daz)
     if (want_p) {
         // both halves of a row, then the 8 neighbour rows of the sample; d p = - d (x_I - p)
         dax += __shfl_xor(dax, 32); day += __shfl_xor(day, 32); daz += __shfl_xor(daz, 32);
@@ -691,8 +579,6 @@ __global__ __launch_bounds__(512) void k_relpos_interp_bwd(LkRelposBwdArgs rb, L
 #define RPF_XU 56                                            // staged input units: 0..51 real, 52 = 1, 53..55 = 0
 #define RPF_DU 64                                            // staged d hid units: two 32-unit blocks at a time
 #define RPF_STAGE_HALVES ((2 * RPF_XU + 2 * RPF_DU) * 32)    // per wave: x pieces [2][56][32] + d hid pieces [2][64][32]
-#define RPF_SC 1024.0f
-#define RPF_ISC (1.0f / 1024.0f)
 
 // lane-dependent parts of the image addresses (in halves), computed once per wave: everything else is a compile-time constant
 struct RpfLane {
@@ -738,27 +624,9 @@ template <bool WG, bool F16>     // F16: half feature tables, a template as in r
 __device__ __forceinline__ void relpos_bwd_wave_fused(const LkRelposBwdArgs& a, int sample0, int P_live, float* __restrict__ part,
                                                       uint16_t* __restrict__ stage_wg, int w, f32x16 (&acc)[2]) {
     const int lane = lk_opaque(lk_lane());            // per tile: see lk_opaque
-    const int h = lane >> 5;
-    const int j = lane & 31;
-    const int sample = sample0 + (j >> 3);
-    const bool live = sample < P_live;
-    const int sp = live ? sample : P_live - 1;
-    const int nb_i = j & 7;
-    const int r = sp / a.S;
-    const float z = a.z[sp];
-    const float px = lk_madd_rn(a.rays_o[3 * r], a.rays_d[3 * r], z);
-    const float py = lk_madd_rn(a.rays_o[3 * r + 1], a.rays_d[3 * r + 1], z);
-    const float pz = lk_madd_rn(a.rays_o[3 * r + 2], a.rays_d[3 * r + 2], z);
-    int idx = a.nbr_idx[(size_t)sp * LK_K + nb_i];
-    const bool has = a.nbr_count[sp] >= a.min_nn;
-    const float wgt = (idx >= 0 && has && live) ? a.nbr_w[(size_t)sp * LK_K + nb_i] : 0.0f;
-    if (idx < 0) idx = 0;
-    const float a0 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx], px));
-    const float a1 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 1], py));
-    const float a2 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 2], pz));
+    RP_ROW_SETUP(a, sample0, P_live, lane, true)
     const float* __restrict__ W = a.W;
     const u32x4* __restrict__ FH = reinterpret_cast<const u32x4*>(a.Wfrag) + FRAGB_U4;
-    const size_t frow = (size_t)idx * LK_C;
     uint16_t* __restrict__ stage = stage_wg + w * RPF_STAGE_HALVES;
     uint16_t* __restrict__ xt_hi = stage;
     uint16_t* __restrict__ xt_lo = stage + RPF_XU * 32;
@@ -766,37 +634,8 @@ __device__ __forceinline__ void relpos_bwd_wave_fused(const LkRelposBwdArgs& a, 
     uint16_t* __restrict__ dt_lo = dt_hi + RPF_DU * 32;
     const RpfLane RL = rpf_lane(lane);
     // ---- recompute the forward of this tile; the fp16 pieces of x go to the LDS image on the way
-    f32x16 x0, x1;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int u0 = 8 * g + 4 * h;
-        if (u0 < ER) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x0[4 * g + t] = rp_embed_unit(W + R_EB, u0 + t, a0, a1, a2);
-        } else {
-            const float4 v = lk_feat4(a.col_feats, F16, frow + (u0 - ER));
-            x0[4 * g] = v.x; x0[4 * g + 1] = v.y; x0[4 * g + 2] = v.z; x0[4 * g + 3] = v.w;
-        }
-    }
-    x1 = lk_zero16();
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int u0 = 32 + 8 * g + 4 * h;
-        if (u0 < KR) {
-            const float4 v = lk_feat4(a.col_feats, F16, frow + (u0 - ER));
-            x1[4 * g] = v.x; x1[4 * g + 1] = v.y; x1[4 * g + 2] = v.z; x1[4 * g + 3] = v.w;
-        }
-    }
-    // derivative of embedding unit u = (+/-) the forward value of its partner unit u +/- 10 (see relpos_bwd_wave): taken now,
-    // x0 is dead after the forward products
-    float fder[12];
-    {
-        const float r0 = __shfl_xor(h ? x0[4] : x0[8], 32), r1 = __shfl_xor(h ? x0[5] : x0[9], 32);
-        const float r2 = __shfl_xor(x0[2], 32), r3 = __shfl_xor(x0[3], 32);
-        fder[0] = x0[6]; fder[1] = x0[7]; fder[2] = r0; fder[3] = r1;
-        fder[4] = h ? -r2 : x0[10]; fder[5] = h ? -r3 : x0[11]; fder[6] = -x0[0]; fder[7] = -x0[1];
-        fder[8] = -r2; fder[9] = -r3; fder[10] = -x0[4]; fder[11] = -x0[5];
-    }
+    RP_INPUT_TILES(x0, x1, W, a.col_feats, F16, false)
+    const RpFder fder = rp_fder(x0, h);              // taken now: x0 is dead after the forward products
     f32x16 hid[4];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) hid[nb] = lk_rowvec_tile(W + R_B1, nb * 32, lane);
@@ -833,10 +672,7 @@ __device__ __forceinline__ void relpos_bwd_wave_fused(const LkRelposBwdArgs& a, 
         const float4 v = *reinterpret_cast<const float4*>(dcrow + 8 * g + 4 * h);
         dout[4 * g] = v.x * wsc; dout[4 * g + 1] = v.y * wsc; dout[4 * g + 2] = v.z * wsc; dout[4 * g + 3] = v.w * wsc;
     }
-    if (WG) {   // linear2 is reduced per SAMPLE (see relpos_bwd_wave): weight sum and weighted hidden vector
-        const float wsum = lk_sum8<true>(wgt);
-        if (live && h == 0 && nb_i == 0) a.w_sum[sp] = wsum;
-    }
+    if (WG) RP_STORE_WSUM(a)                          // linear2 is reduced per SAMPLE: weight sum and, below, weighted hidden vector
     // ---- d hid = (W2^T d out) * softplus'(hid), block by block in place of hid
     f32x16 (&dhid)[4] = hid;
     const LkH8 db0 = lk_split_cth(dout, 0), db1 = lk_split_cth(dout, 1);
@@ -851,16 +687,7 @@ __device__ __forceinline__ void relpos_bwd_wave_fused(const LkRelposBwdArgs& a, 
             fa1 = lk_fragh_load(FH + FM21_TRH, 4, 1, nb + 1, lane);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (WG) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float v[4];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) v[tt] = lk_sum8<true>(wgt * hid[nb][4 * g + tt]);
-                if (live && nb_i == 0)
-                    *reinterpret_cast<float4*>(a.hbar + (size_t)sp * 128 + nb * 32 + 8 * g + 4 * h) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-        }
+        if (WG) { RP_STORE_HBAR(a, hid, nb) }
 #pragma unroll
         for (int q = 0; q < 16; ++q) dhid[nb][q] = t[q] * lk_softplus100_grad_from_out(hid[nb][q]);
     }
@@ -909,33 +736,8 @@ __device__ __forceinline__ void relpos_bwd_wave_fused(const LkRelposBwdArgs& a, 
         __builtin_amdgcn_sched_barrier(0);
     }
     // ---- d B (Fourier matrix) and the d feature rows, from d x / 2^10
-#pragma unroll
-    for (int tile = 0; tile < 2; ++tile)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int u0 = 32 * tile + 8 * g + 4 * h;
-            const bool is_emb = u0 < ER;
-            if (tile == 0 && g < 3) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int u = u0 + t;
-                    const int xi = is_emb ? ((u < 10) ? u : u - 10) : 0;
-                    float gx = 0.0f;
-                    if (is_emb) gx = dx[tile][4 * g + t] * RPF_ISC * fder[4 * g + t];
-                    const float s0 = lk_half_wave_sum(gx * a0), s1 = lk_half_wave_sum(gx * a1), s2 = lk_half_wave_sum(gx * a2);
-                    if ((lane & 31) == LK_HWS_LANE && is_emb) {
-                        atomicAdd(part + xi, s0);
-                        atomicAdd(part + 10 + xi, s1);
-                        atomicAdd(part + 20 + xi, s2);
-                    }
-                }
-            }
-            if (!is_emb && u0 < KR) {
-                if ((a.flags & LK_FLAG_GRAD_FEATS) && live)
-                    *reinterpret_cast<float4*>(a.dfeat + ((size_t)sp * 8 + nb_i) * LK_C + (u0 - ER)) =
-                        make_float4(dx[tile][4 * g] * RPF_ISC, dx[tile][4 * g + 1] * RPF_ISC, dx[tile][4 * g + 2] * RPF_ISC, dx[tile][4 * g + 3] * RPF_ISC);
-            }
-        }
+    float none = 0.0f;                                // (no d p here)
+    RP_TAIL(a, dx, fder, true, false, false, true, part, none, none, none)
 }
 
 template <bool WG, bool F16>

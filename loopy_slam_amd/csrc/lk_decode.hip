@@ -14,6 +14,7 @@
 #include "lk_common.h"
 #include "lk_kernels.h"
 #include "lk_composite_dev.h"
+#include "lk_relpos_dev.h"
 #include <string.h>
 
 using namespace lkw;
@@ -73,14 +74,6 @@ __device__ __forceinline__ f32x16 geo_embed_tile(const float* __restrict__ B, in
     return e;
 }
 
-// [sin(x_0..n-1), cos(x_0..n-1)] embedding unit u of a [3][n] matrix (colour: n = 20, rel-pos: n = 10)
-__device__ __forceinline__ float sincos_embed_unit(const float* __restrict__ B, int n, int u, float a0, float a1, float a2) {
-    if (u >= 2 * n) return 0.0f;
-    const int xi = (u < n) ? u : u - n;
-    const float x = lk_fourier_arg(a0, a1, a2, B[xi], B[n + xi], B[2 * n + xi]);
-    return (u < n) ? lk_sinf(x) : lk_cosf(x);
-}
-
 template <int NG>
 __device__ __forceinline__ f32x16 sincos_embed_tile(const float* __restrict__ B, int n, int b, float a0, float a1, float a2, int lane) {
     const int h = lane >> 5;
@@ -89,7 +82,7 @@ __device__ __forceinline__ f32x16 sincos_embed_tile(const float* __restrict__ B,
     for (int g = 0; g < NG; ++g)
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-            e[4 * g + t] = sincos_embed_unit(B, n, 32 * b + 8 * g + 4 * h + t, a0, a1, a2);
+            e[4 * g + t] = sincos_embed_unit<true>(B, n, 32 * b + 8 * g + 4 * h + t, a0, a1, a2);
     return e;
 }
 
@@ -370,10 +363,10 @@ __device__ __forceinline__ void decode_col_setup(const LkDecodeArgs& a, int tile
     // barriers later) - 4 to 8 evaluations per lane instead of 20, a fifth of the kernel's VALU instructions.
     float ev[4], e1v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int t = 0; t < 4; ++t) ev[t] = sincos_embed_unit(W + C_EB, 20, 8 * w + 4 * h + t, a0, a1, a2);
+    for (int t = 0; t < 4; ++t) ev[t] = sincos_embed_unit<true>(W + C_EB, 20, 8 * w + 4 * h + t, a0, a1, a2);
     if (w == 3) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) e1v[t] = sincos_embed_unit(W + C_EB, 20, 32 + 4 * h + t, a0, a1, a2);
+        for (int t = 0; t < 4; ++t) e1v[t] = sincos_embed_unit<true>(W + C_EB, 20, 32 + 4 * h + t, a0, a1, a2);
     }
     if (save && live) {              // embedding rows 0..39 (input of layers 0 and 3) for the weight gradients
         float* erow = a.act + (size_t)a.P * (LK_ACT_GEO_A + LK_ACT_COL_A + LK_ACT_COL_H) + (size_t)sp * LK_ACT_COL_E;
@@ -619,70 +612,22 @@ __global__ __launch_bounds__(256, 2) void k_decode_fwd(LkDecodeArgs a, int n_col
 template <bool CHECK = false>
 __device__ __forceinline__ void relpos_fwd_wave(const LkRelposArgs& a, int sample0, int P) {
     const int lane = lk_lane();
-    const int h = lane >> 5;
-    const int j = lane & 31;                    // row of the tile: sample j>>3, neighbour j&7
-    const int sample = sample0 + (j >> 3);
-    const bool live = sample < P;
-    const int sp = live ? sample : P - 1;
-    const int nb_i = j & 7;
-    const int r = sp / a.S;
-    const float z = a.z[sp];
-    const float px = lk_madd_rn(a.rays_o[3 * r], a.rays_d[3 * r], z);
-    const float py = lk_madd_rn(a.rays_o[3 * r + 1], a.rays_d[3 * r + 1], z);
-    const float pz = lk_madd_rn(a.rays_o[3 * r + 2], a.rays_d[3 * r + 2], z);
-    int idx = a.nbr_idx[(size_t)sp * LK_K + nb_i];
-    const float wgt = (idx >= 0) ? a.nbr_w[(size_t)sp * LK_K + nb_i] : 0.0f;
-    if (idx < 0) idx = 0;                       // padded slot: finite dummy row, weight 0
-    // D = x_I - p (decoder.py:478-479); arguments a_i = fl(2 pi D_i)
-    const float a0 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx], px));
-    const float a1 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 1], py));
-    const float a2 = __fmul_rn(LK_TWO_PI, __fsub_rn(a.pos[3 * (size_t)idx + 2], pz));
+    RP_ROW_SETUP(a, sample0, P, lane, false)         // the weight of every filled slot: `has` is applied where c is stored
     const float* __restrict__ W = a.W;
     const u32x4* __restrict__ FB = reinterpret_cast<const u32x4*>(a.Wfrag) + FRAGB_U4;      // fp16 forward fragments
-    const size_t frow = (size_t)idx * LK_C;
-    const bool f16 = a.feats_f16 != 0;
-    // X^T tiles: units 0..19 embedding, 20..51 feature channels 0..31, 52..55 zero
-    f32x16 x0, x1;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int u0 = 8 * g + 4 * h;
-        if (u0 < ER) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x0[4 * g + t] = sincos_embed_unit(W + R_EB, 10, u0 + t, a0, a1, a2);
-        } else {
-            const float4 v = lk_feat4(a.col_feats, f16, frow + (u0 - ER));
-            x0[4 * g] = v.x; x0[4 * g + 1] = v.y; x0[4 * g + 2] = v.z; x0[4 * g + 3] = v.w;
-        }
-    }
-    x1 = lk_zero16();
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int u0 = 32 + 8 * g + 4 * h;
-        if (u0 < KR) {
-            const float4 v = lk_feat4(a.col_feats, f16, frow + (u0 - ER));
-            x1[4 * g] = v.x; x1[4 * g + 1] = v.y; x1[4 * g + 2] = v.z; x1[4 * g + 3] = v.w;
-        }
-    }
+    RP_INPUT_TILES(x0, x1, W, a.col_feats, a.feats_f16 != 0, true)
     ct_check_range<CHECK>(x0, a.status); ct_check_range<CHECK>(x1, a.status);
     LK_STAMPW(1);                                    // (probe build) lists, positions and feature rows arrived, embedding evaluated
-    f32x16 hid[4];
+    RP_HIDDEN(hid, W, FB, x0, x1, lane)
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb) hid[nb] = lk_rowvec_tile(W + R_B1, nb * 32, lane);      // accumulators start from the bias
-    lk_gemm_h3<4, 2>(hid, FB + FM20_FWDH, 4, 0, 0, x0, 0, lane);
-    lk_gemm_h3<4, 2>(hid, FB + FM20_FWDH, 4, 2, 0, x1, 0, lane);       // units 32..55; registers 12..15 of x1 are zero
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) hid[nb][q] = lk_softplus100(hid[nb][q]);
-        ct_check_range<CHECK>(hid[nb], a.status);
-    }
+    for (int nb = 0; nb < 4; ++nb) ct_check_range<CHECK>(hid[nb], a.status);
     LK_STAMP(2);
     f32x16 out[1];
     out[0] = lk_rowvec_tile(W + R_B2, 0, lane);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) lk_gemm_h3<1, 2>(out, FB + FM21_FWDH, 1, 2 * kb, 0, hid[kb], 0, lane);
     // c[ch] = sum over the 8 neighbour rows of a sample (8 consecutive lanes) of w * f[ch]
-    const bool has = a.nbr_count[sp] >= a.min_nn;
+    const bool kept = rp_has(a, sp);
     float* __restrict__ crow = a.c_col + (size_t)sp * LK_C;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -696,7 +641,7 @@ __device__ __forceinline__ void relpos_fwd_wave(const LkRelposArgs& a, int sampl
         if (live && nb_i == 0) {
             const int ch = 8 * g + 4 * h;
             float4 o = make_float4(v[0], v[1], v[2], v[3]);
-            if (!has) o = a.noise_col ? *reinterpret_cast<const float4*>(a.noise_col + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!kept) o = a.noise_col ? *reinterpret_cast<const float4*>(a.noise_col + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(crow + ch) = o;
         }
     }
