@@ -718,6 +718,32 @@ int lk_mesh_depth_setup(const float* verts, int64_t V, const int32_t* faces, int
 int lk_mesh_depth_raster(const float* rec, const int32_t* box, const int32_t* tile_end, int64_t F, int64_t T, int32_t H, int32_t W, float fx,
                          float fy, float cx, float cy, float near, float far, float* depth /*[H,W]*/, void* stream);
 
+/* ---------------------------------------------------------------- rendering evaluation
+ * The image figures the reference reports for every re-rendered frame (src/Mapper.py:1120-1160): depth L1 and PSNR over the pixels with a
+ * sensor depth, and MS-SSIM as pytorch_msssim.ms_ssim(X, Y, data_range=1.0, size_average=True) forms it.  The device produces sums and means;
+ * the caller combines them (loopy_slam_amd/render_eval.py).  No floating-point atomic: per-workgroup partials and a fixed-order reduction, so
+ * two calls on equal inputs give equal bits.  ws: lk_img_eval_ws_bytes(H, W) bytes, 8-byte aligned; its contents on entry do not matter.
+ *
+ * out_rec[LK_IMG_REC] (fp64, device):
+ *   [0]  n_valid: the number of pixels with gt_depth > 0 (exact)
+ *   [1]  sum over those pixels of |fl32(gt_depth - depth)|
+ *   [2]  sum over those pixels and the three channels of fl32(gt_color - color)^2
+ *        (the difference is one fp32 subtraction; widened to fp64 it is made absolute or squared - exact - and added in fp64)
+ *   [3 + 6 l + c], [3 + 6 l + 3 + c]   level l = 0 .. 4, channel c = 0 .. 2: the mean of the SSIM map and of the contrast-structure map
+ *        (with_msssim = 0: neither computed nor written)
+ * Level l + 1 is the 2 x 2 average of level l with stride 2 and one line of zeros in FRONT of every odd-sized dimension, divisor always 4
+ * (avg_pool2d(kernel_size=2, padding=size % 2)): size s becomes (s + 1) / 2.  Per level and channel, with G the 11-tap window
+ * g[k] = exp(-(k - 5)^2 / (2 1.5^2)) / sum (formed in fp64, rounded to fp32) applied down the columns and then along the rows without
+ * padding (an h x w level has (h - 10) x (w - 10) maps), C1 = 0.01^2, C2 = 0.03^2:
+ *   mu1 = G(X), mu2 = G(Y), s1 = G(X X) - mu1^2, s2 = G(Y Y) - mu2^2, s12 = G(X Y) - mu1 mu2,
+ *   cs = (2 s12 + C2) / (s1 + s2 + C2), ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) cs
+ * in fp32 with every operation rounded once and each window sum taken in tap order; the map sums are fp64.  MS-SSIM is defined for
+ * min(H, W) > 160 only (the package's assertion): with_msssim != 0 on a smaller image is an error.  3 H W < 2^31. */
+#define LK_IMG_REC 33
+int lk_img_eval_ws_bytes(int32_t H, int32_t W, int64_t* out_bytes);
+int lk_img_eval(const float* gt_color, const float* color /*[H][W][3], values in [0, 1]*/, const float* gt_depth, const float* depth /*[H][W]*/,
+                int32_t H, int32_t W, int32_t with_msssim, void* ws, double* out_rec /*device, [LK_IMG_REC]*/, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -39,6 +39,7 @@ EXPOSURE_MAX_F = 32
 ICP_POINT_TO_PLANE, ICP_INFORMATION, ICP_SUMS = 0, 1, 32
 FPFH_DIM, RANSAC_BEST = 33, 20
 ADAM_MAX_SEG = 16
+IMG_REC = 33
 
 _fp = C.c_void_p     # every device pointer crosses the ABI as an integer address
 
@@ -242,6 +243,8 @@ class LoopyLib:
                                      C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_mesh_depth_raster', [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_float, C.c_float, _fp, C.c_void_p], C.c_int),
+            ('lk_img_eval_ws_bytes', [C.c_int32, C.c_int32, C.POINTER(C.c_int64)], C.c_int),
+            ('lk_img_eval', [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

@@ -10,7 +10,8 @@
 All arithmetic of the hot path runs in libloopyhip (loopy_slam_amd.core / .steps / .optim); what remains here is
 per-frame bookkeeping in torch.  Loop closure's geometric back end (segment registration, pose graph, map correction) is
 loop_closure.py, off by default (cfg['loop_closure']['enabled']); the final mesh (TSDF fusion of the mapped frames + marching
-cubes) is tsdf.py, off by default (cfg['meshing']['enabled']); place recognition stays out of scope, as do datasets and
+cubes) is tsdf.py, off by default (cfg['meshing']['enabled']); the evaluation of the re-rendered frames and of the trajectory is
+render_eval.py, off by default (cfg['rendering_eval']['enabled']); place recognition stays out of scope, as do datasets and
 visualisation (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
 the default is the gfx950 library on the current CUDA device.
 """
@@ -491,6 +492,13 @@ class Mapper:
         if self.meshing and getattr(getattr(slam, 'dist', None), 'world', 1) > 1:
             raise NotImplementedError('meshing.enabled with world > 1: the fusion runs on one rank - mesh the checkpoint afterwards '
                                       '(tools/get_mesh_tsdf_fusion.py)')
+        # rendering evaluation (render_eval.py; off unless cfg['rendering_eval']['enabled']): at the end of run() the mapped frames are
+        # re-rendered and measured against the input (depth L1, PSNR, MS-SSIM), with the ATE of the trajectory, into eval/rendering.json
+        self.rendering_eval = bool((cfg.get('rendering_eval') or {}).get('enabled'))
+        self.eval_result = None
+        if self.rendering_eval and getattr(getattr(slam, 'dist', None), 'world', 1) > 1:
+            raise NotImplementedError('rendering_eval.enabled with world > 1: the evaluation runs on one rank - evaluate the checkpoint '
+                                      'afterwards (tools/eval_rendering.py)')
         self.segment_strategy = m.get('segment_strategy', 'rot_trans')
         self.segment_rot_cos, self.segment_rel_trans = m.get('segment_rot_cos', 0.94), m.get('segment_rel_trans', 0.30)
         self.fixed_segment_size = m.get('fixed_segment_size', 50)
@@ -799,9 +807,15 @@ class Mapper:
             if self.cfg.get('stop') and idx != 0 and idx % self.cfg['stop'] == 0:       # Tracker.py:423, Mapper.py:1048 (run.py --stop)
                 n = idx + 1
                 break
+        records = None
+        if self.rendering_eval:
+            from . import render_eval
+            records = render_eval.FrameRecords(self)
         if self.meshing:                        # Mapper.py:1080-1200: re-render the mapped frames, fuse them, write the mesh
             from . import tsdf
-            self.mesh_file, _ = tsdf.mesh_run(self, n)
+            self.mesh_file, _ = tsdf.mesh_run(self, n, on_frame=records)     # (a frame re-rendered for the mesh is measured there)
+        if self.rendering_eval:                 # Mapper.py:1056-1160: ATE, depth L1, PSNR and MS-SSIM of the re-rendered frames
+            self.eval_result = render_eval.eval_run(self, n, records=records)
         return slam.estimate_c2w_list[:n], slam.gt_c2w_list[:n]
 
 

@@ -261,11 +261,12 @@ def rendered_frame(mapper, idx, gt_color, gt_depth, c2w):
     return depth, color.float()
 
 
-def fuse_run(mapper, n_frames, ms=None, save_dir=None):
+def fuse_run(mapper, n_frames, ms=None, save_dir=None, on_frame=None):
     """Every mapped frame (idx % every_frame == 0) below n_frames fused at its final estimate_c2w_list pose - loop-closure corrections and the
     final refinement included - from the re-rendered ('rendered') or the input ('sensor') depth and colour.  save_dir: the re-rendered frames
     are also kept there as depth_XXXXX.npy / color_XXXXX.npy (the reference's rendered_every_frame folder, Mapper.py:1116-1119: what
-    tools/get_mesh_tsdf_fusion.py reads).  Returns the volume."""
+    tools/get_mesh_tsdf_fusion.py reads).  on_frame(idx, gt_color, gt_depth, depth, color) is called with every re-rendered frame (the
+    rendering evaluation's hook: one render serves both).  Returns the volume."""
     s = mapper.slam
     ms = ms or settings(mapper.cfg)
     vol = TSDFVolume(mapper.eng, voxel_length=ms['voxel_length'], sdf_trunc=ms['sdf_trunc'])
@@ -275,7 +276,10 @@ def fuse_run(mapper, n_frames, ms=None, save_dir=None):
         if not bool(torch.isfinite(c2w).all()):
             continue
         if ms['source'] == 'rendered':
-            depth, color = rendered_frame(mapper, idx, color, depth, c2w.to(mapper.eng.device))
+            gt_color, gt_depth = color, depth
+            depth, color = rendered_frame(mapper, idx, gt_color, gt_depth, c2w.to(mapper.eng.device))
+            if on_frame is not None:
+                on_frame(idx, gt_color, gt_depth, depth, color)
             if save_dir is not None:
                 os.makedirs(save_dir, exist_ok=True)
                 np.save(os.path.join(save_dir, f'depth_{idx:05d}'), depth.cpu().numpy())
@@ -284,9 +288,10 @@ def fuse_run(mapper, n_frames, ms=None, save_dir=None):
     return vol
 
 
-def mesh_run(mapper, n_frames, output=None):
+def mesh_run(mapper, n_frames, output=None, on_frame=None):
     """fuse_run + extract_triangle_mesh + write_ply to {output}/mesh/{scene}_pred_mesh.ply; returns (path, mesh)."""
     path = mesh_path(mapper.cfg, output)
-    mesh = fuse_run(mapper, n_frames, save_dir=os.path.join(os.path.dirname(os.path.dirname(path)), 'rendered_every_frame')).extract_triangle_mesh()
+    mesh = fuse_run(mapper, n_frames, save_dir=os.path.join(os.path.dirname(os.path.dirname(path)), 'rendered_every_frame'),
+                    on_frame=on_frame).extract_triangle_mesh()
     write_ply(path, mesh)
     return path, mesh
