@@ -261,6 +261,13 @@ struct LkFeatScatterArgs {
 int lk_launch_seg_sort(const LkFeatScatterArgs& a, bool counted, hipStream_t st, int batch = 1);        // counted: k_sample_interp already ran the count pass
 int lk_launch_scan_i32(int32_t* data, int32_t* out, int32_t* block_sums, int total, hipStream_t st,
                        int batch = 1, int dstride = 0, int sstride = 0);   // out != data: data is cleared; batch members y at + y * stride
+int lk_launch_carry_scan_total(int32_t* counts, int n, int32_t* out_total, hipStream_t st);   // one 1024-thread workgroup, in place (lk_knn.hip)
+// stable compaction of a byte mask (lk_optim.hip): one 1024-thread workgroup / count, scan, scatter over 256-entry blocks (block_scratch:
+// ceil(n / 256) ints) / the first up to LK_COMPACT_ONE_BLOCK_MAX entries, the second above.  Same result.
+#define LK_COMPACT_ONE_BLOCK_MAX 16384
+int lk_launch_compact(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, hipStream_t st);
+int lk_launch_compact_mb(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, hipStream_t st);
+int lk_launch_compact_any(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, hipStream_t st);
 
 struct LkRaysBwdArgs { int R, S; const float* z; const float* dp_total; float* g_rays_o; float* g_rays_d; };
 

@@ -3,7 +3,9 @@
 // 1623-1627, 1659-1708).  Build = device-only counting sort (AABB reduce -> cell histogram
 // -> exclusive scan -> scatter), no host synchronisation, graph-capturable.
 #include "lk_common.h"
+#include "lk_kernels.h"
 #include "lk_knn_dev.h"
+#include "lk_scan_dev.h"
 
 #include <limits.h>
 
@@ -103,16 +105,10 @@ __global__ __launch_bounds__(256) void k_scan_block(int32_t* data, int32_t* out,
 #pragma unroll
     for (int q = 0; q < 4; ++q) v[q] = (idx + q < total) ? data[idx + q] : 0;
     const int s = v[0] + v[1] + v[2] + v[3];
-    int incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int nb = __shfl_up(incl, o);
-        if (lane >= o) incl += nb;
-    }
+    const int incl = lk_wave_incl_scan(s, lane);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
-    int woff = 0;
-    for (int q = 0; q < w; ++q) woff += wsum[q];
+    const int woff = lk_waves_before(wsum, w, 0);
     int run = woff + incl - s;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -125,33 +121,32 @@ __global__ __launch_bounds__(256) void k_scan_block(int32_t* data, int32_t* out,
     if (t == 255) block_sums[blockIdx.x] = woff + incl;
 }
 
-// exclusive scan of the block totals (single block, 256 at a time with a running carry)
-__global__ __launch_bounds__(256) void k_scan_sums(int32_t* __restrict__ block_sums, const LkGrid* __restrict__ g, int total_host, int sstride) {
-    __shared__ int wsum[4];
+// in-place exclusive scan of the block totals of `total` items at ITEMS per block: a single workgroup, NT at a time with a running carry
+// (g / total_host as k_scan_block; blockIdx.x: batch member, sstride apart; TOTAL: the sum of them all goes to *out_total)
+// <256, SCAN_ITEMS, false>: the block sums of k_scan_block; <1024, 1, true>: the block counts of the many-block compaction (lk_optim.hip)
+template <int NT, int ITEMS, bool TOTAL>
+__global__ __launch_bounds__(NT) void k_carry_scan(int32_t* __restrict__ block_sums, const LkGrid* __restrict__ g, int total_host, int sstride,
+                                                  int32_t* __restrict__ out_total) {
+    __shared__ int wsum[NT / 64];
     __shared__ int carry;
     block_sums += (size_t)blockIdx.x * sstride;              // one workgroup per batch member
-    const int nb = ((g ? g->ncells + 1 : total_host) + SCAN_ITEMS - 1) / SCAN_ITEMS;
+    const int nb = ((g ? g->ncells + 1 : total_host) + ITEMS - 1) / ITEMS;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (t == 0) carry = 0;
     __syncthreads();
-    for (int base = 0; base < nb; base += 256) {
+    for (int base = 0; base < nb; base += NT) {
         const int i = base + t;
         const int s = (i < nb) ? block_sums[i] : 0;
-        int incl = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int nbv = __shfl_up(incl, o);
-            if (lane >= o) incl += nbv;
-        }
+        const int incl = lk_wave_incl_scan(s, lane);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
-        int woff = carry;
-        for (int q = 0; q < w; ++q) woff += wsum[q];
+        const int woff = lk_waves_before(wsum, w, carry);
         if (i < nb) block_sums[i] = woff + incl - s;
         __syncthreads();
-        if (t == 255) carry = woff + incl;
+        if (t == NT - 1) carry = woff + incl;
         __syncthreads();
     }
+    if (TOTAL && t == 0) *out_total = carry;
 }
 
 __global__ __launch_bounds__(256) void k_scan_add(int32_t* __restrict__ data, const int32_t* __restrict__ block_sums,
@@ -211,9 +206,14 @@ int lk_launch_scan_i32(int32_t* data, int32_t* out, int32_t* block_sums, int tot
     const int nb = lk_cdiv(total, SCAN_ITEMS);
     hipLaunchKernelGGL(k_scan_block, dim3(nb, batch), dim3(256), 0, st, data, out, block_sums, (const LkGrid*)nullptr, total, dstride, sstride);
     if (nb > 1) {
-        hipLaunchKernelGGL(k_scan_sums, dim3(batch), dim3(256), 0, st, block_sums, (const LkGrid*)nullptr, total, sstride);
+        hipLaunchKernelGGL((k_carry_scan<256, SCAN_ITEMS, false>), dim3(batch), dim3(256), 0, st, block_sums, (const LkGrid*)nullptr, total, sstride, (int32_t*)nullptr);
         hipLaunchKernelGGL(k_scan_add, dim3(nb, batch), dim3(256), 0, st, out, (const int32_t*)block_sums, (const LkGrid*)nullptr, total, dstride, sstride);
     }
+    return LK_OK;
+}
+// in-place exclusive scan of n counts by one 1024-thread workgroup, their sum to *out_total
+int lk_launch_carry_scan_total(int32_t* counts, int n, int32_t* out_total, hipStream_t st) {
+    hipLaunchKernelGGL((k_carry_scan<1024, 1, true>), dim3(1), dim3(1024), 0, st, counts, (const LkGrid*)nullptr, n, 0, out_total);
     return LK_OK;
 }
 
@@ -301,7 +301,7 @@ extern "C" int lk_knn_build(lk_knn_t h, const float* pos, int64_t N, void* strea
         hipLaunchKernelGGL(k_count, dim3(lk_cdiv(n, 256)), dim3(256), 0, st, pos, n, h->grid, h->cell_start,
                            h->cell_of, h->rank_of);
         hipLaunchKernelGGL(k_scan_block, dim3(h->n_scan_blocks), dim3(256), 0, st, h->cell_start, h->cell_start, h->block_sums, h->grid, 0, 0, 0);
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, h->block_sums, h->grid, 0, 0);
+        hipLaunchKernelGGL((k_carry_scan<256, SCAN_ITEMS, false>), dim3(1), dim3(256), 0, st, h->block_sums, h->grid, 0, 0, (int32_t*)nullptr);
         hipLaunchKernelGGL(k_scan_add, dim3(h->n_scan_blocks), dim3(256), 0, st, h->cell_start, h->block_sums, h->grid, 0, 0, 0);
         hipLaunchKernelGGL(k_scatter, dim3(lk_cdiv(n, 256)), dim3(256), 0, st, pos, n, h->cell_start, h->cell_of,
                            h->rank_of, h->sorted);

@@ -71,7 +71,7 @@ __device__ __forceinline__ void pregather_ray(const LkPregatherArgs& a, size_t b
 }
 template <int VPT>
 __global__ __launch_bounds__(1024) void k_pregather(LkPregatherArgs a) {
-    __shared__ LkMaskShared S;
+    __shared__ LkSelectShared S;
     __shared__ int s_wave[VPT][16];                       // kept rays per (ray group q, wave)
     const int t = threadIdx.x, it = blockIdx.x;
     const size_t base = (size_t)it * a.R;
@@ -115,11 +115,11 @@ __global__ __launch_bounds__(1024) void k_pregather(LkPregatherArgs a) {
     int pre[VPT];                                         // kept rays before this one inside its (q, wave)
 #pragma unroll
     for (int q = 0; q < VPT; ++q) {
-        const unsigned long long bal = __ballot(keep[q]);
-        pre[q] = __popcll(bal & ((1ull << lane) - 1ull));
+        const unsigned long long bal = lk_ballot_rank(keep[q], lane, pre[q]);
         if (lane == 0) s_wave[q][wv] = __popcll(bal);
     }
     __syncthreads();
+    // (not lk_waves_before: all 16 counts are read, masked, because their sum is needed as well)
     int before_q = 0, n_keep = 0;                         // kept rays in the (q', wave') pairs before (q, wv); total
     int off[VPT];
 #pragma unroll
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void k_track_composite(LkTrackLossArgs a) {
 // pass 2 - mask by 10 x the batch mean, loss terms (Tracker.py:169-191), d depth / d colour and the composite's backward for them - is the
 // prologue of k_decode_bwd (lk_track_draw, lk_track_dev.h); with tracking.handle_dynamic: False the threshold is the median's:
 __global__ __launch_bounds__(1024) void k_track_median(LkTrackLossArgs a) {
-    __shared__ LkMedianShared S;
+    __shared__ LkSelectShared S;
     const float thr = lk_block_median10(a.resid, a.R, S);
     if (threadIdx.x == 0) a.part[0] = thr;
 }

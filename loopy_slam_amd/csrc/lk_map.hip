@@ -4,12 +4,11 @@
 // Both are HBM-bound index work: one thread per point / ray, coalesced 12-byte position reads, the radius test on
 // the same uniform grid as the renderer's kNN, stable ballot + prefix-sum compaction (k_compact).
 #include "lk_common.h"
+#include "lk_kernels.h"
 #include "lk_knn_dev.h"
+#include "lk_scan_dev.h"
 
 #include <math.h>
-
-int lk_launch_compact(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, hipStream_t st);
-int lk_launch_compact_mb(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, hipStream_t st);
 
 // ------------------------------------------------------------------ frustum rows
 struct LkFrustumArgs {
@@ -99,8 +98,7 @@ extern "C" int lk_frustum_rows(const float* pos, int32_t N, const float* w2c12_h
     hipLaunchKernelGGL(k_frustum_sample, dim3(lk_cdiv(N, 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_frustum_mask, dim3(lk_cdiv(N, 256)), dim3(256), 0, st, a);
     // the sampled-depth scratch is dead after the mask pass: reuse it for the per-block counts of the compaction
-    if (N > 16384) lk_launch_compact_mb(scratch_mask, N, out_index, out_count, reinterpret_cast<int32_t*>(scratch_depth), st);
-    else lk_launch_compact(scratch_mask, N, out_index, out_count, st);
+    lk_launch_compact_any(scratch_mask, N, out_index, out_count, reinterpret_cast<int32_t*>(scratch_depth), st);
     LK_LAUNCH_CHECK();
     return LK_OK;
 }
@@ -257,86 +255,49 @@ extern "C" int lk_radius_maps(const float* color, int32_t H, int32_t W, double c
 __global__ __launch_bounds__(1024) void k_top_grad(const float* __restrict__ grad, int n, int K, int W, int H0, int H1, int W0, int W1,
                                                    const float* __restrict__ depth, int depth_limit,
                                                    int32_t* __restrict__ out_index, int32_t* __restrict__ out_count) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_prefix, s_rank, s_above;
+    __shared__ LkSelectShared S;                                    // s_cnt: pixels above the cut
     __shared__ int wa[16], wb[16];
     __shared__ int s_ties_seen, s_out;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) { s_prefix = 0; s_rank = (unsigned)(n - K); s_above = 0; s_ties_seen = 0; s_out = 0; }   // ascending rank of the K-th largest
-    __syncthreads();
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (t < 256) hist[t] = 0;
-        __syncthreads();
-        const unsigned prefix = s_prefix;
-        const unsigned himask = (shift == 24) ? 0u : (0xffffffffu << (shift + 8));
+    if (t == 0) { S.s_cnt = 0; s_ties_seen = 0; s_out = 0; }
+    // bit pattern of the K-th largest magnitude = ascending rank n - K.  Few distinct high bytes: the first two passes aggregate
+    LK_RADIX_SELECT(S, t, (unsigned)(n - K), true, if (t < 256) S.hist[t] = 0,
         for (int c0 = 0; c0 < n; c0 += 1024) {
             const int i = c0 + t;
             const unsigned u = (i < n) ? __float_as_uint(grad[i]) : 0u;
             const bool on = (i < n) && (u & himask) == prefix;
             const unsigned digit = (u >> shift) & 255u;
-            if (shift >= 16) {          // few distinct high bytes: one LDS add per (wave, byte)
-                unsigned long long pending = __ballot(on);
-                while (pending) {
-                    const int leader = __ffsll((long long)pending) - 1;
-                    const unsigned dl = __shfl(digit, leader);
-                    const unsigned long long same = __ballot(on && digit == dl);
-                    if (lane == leader) atomicAdd(&hist[dl], (unsigned)__popcll(same));
-                    pending &= ~same;
-                }
-            } else if (on) {
-                atomicAdd(&hist[digit], 1u);
-            }
-        }
-        __syncthreads();
-        if (t < 64) {
-            const unsigned rank = s_rank;
-            const unsigned h0 = hist[4 * t], h1 = hist[4 * t + 1], h2 = hist[4 * t + 2], h3 = hist[4 * t + 3];
-            const unsigned tot = h0 + h1 + h2 + h3;
-            unsigned incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned nbv = __shfl_up(incl, o);
-                if (t >= o) incl += nbv;
-            }
-            const unsigned excl = incl - tot;
-            if (rank >= excl && rank < incl) {
-                unsigned r = rank - excl, b = 4 * t;
-                if (r >= h0) { r -= h0; ++b; if (r >= h1) { r -= h1; ++b; if (r >= h2) { r -= h2; ++b; } } }
-                s_rank = r;
-                s_prefix = prefix | (b << shift);
-            }
-        }
-        __syncthreads();
-    }
-    const unsigned kth = s_prefix;                                  // bit pattern of the K-th largest magnitude
+            if (shift >= 16) LK_HIST_ADD_WAVE(S.hist, on, digit, lane)
+            else if (on) atomicAdd(&S.hist[digit], 1u);
+        })
+    const unsigned kth = S.s_prefix;
     // how many are strictly above it -> how many ties at the cut belong to the pool
     {
         unsigned cnt = 0;
         for (int i = t; i < n; i += 1024) cnt += (__float_as_uint(grad[i]) > kth) ? 1u : 0u;
-        atomicAdd(&s_above, cnt);
+        atomicAdd(&S.s_cnt, cnt);
     }
     __syncthreads();
-    const int ties_needed = K - (int)s_above;
+    const int ties_needed = K - (int)S.s_cnt;
     for (int c0 = 0; c0 < n; c0 += 1024) {
         const int i = c0 + t;
         const unsigned u = (i < n) ? __float_as_uint(grad[i]) : 0u;
         const bool tie = (i < n) && u == kth;
-        const unsigned long long bt = __ballot(tie);
+        int before;
+        const unsigned long long bt = lk_ballot_rank(tie, lane, before);
         if (lane == 0) wa[w] = __popcll(bt);
         __syncthreads();
-        int tie_rank = s_ties_seen + __popcll(bt & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) tie_rank += wa[q];
+        const int tie_rank = lk_waves_before(wa, w, s_ties_seen + before);
         bool member = (i < n) && (u > kth || (tie && tie_rank < ties_needed));
         if (member) {
             const int y = i / W, x = i - y * W;
             member = y >= H0 && y < H1 && x >= W0 && x < W1;
             if (member && depth) { const float d = depth[i]; member = d > 0.0f && (!depth_limit || d <= 5.0f); }
         }
-        const unsigned long long bm = __ballot(member);
+        const unsigned long long bm = lk_ballot_rank(member, lane, before);
         if (lane == 0) wb[w] = __popcll(bm);
         __syncthreads();
-        int off = s_out + __popcll(bm & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) off += wb[q];
+        const int off = lk_waves_before(wb, w, s_out + before);
         if (member) out_index[off] = i;
         __syncthreads();
         if (t == 0) {
@@ -373,21 +334,9 @@ __device__ __forceinline__ void tg_select(const unsigned* __restrict__ hist_all,
     for (int p = 0; p < passes; ++p) {
         const int shift = 24 - 8 * p;
         const unsigned* hist = hist_all + 256 * p;
-        const unsigned h0 = hist[4 * t], h1 = hist[4 * t + 1], h2 = hist[4 * t + 2], h3 = hist[4 * t + 3];
-        const unsigned tot = h0 + h1 + h2 + h3;
-        unsigned incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned nbv = __shfl_up(incl, o);
-            if (t >= o) incl += nbv;
-        }
-        const unsigned excl = incl - tot;
         unsigned r = 0, b = 0;
-        const bool mine = rank >= excl && rank < incl;
-        if (mine) {
-            r = rank - excl; b = 4 * t;
-            if (r >= h0) { r -= h0; ++b; if (r >= h1) { r -= h1; ++b; if (r >= h2) { r -= h2; ++b; } } }
-        }
+        bool mine = false;
+        LK_RADIX_LOCATE(hist, rank, t, bin, rank_in_bin, mine = true; b = bin; r = rank_in_bin;)
         const unsigned long long who = __ballot(mine);
         const int src = __ffsll((long long)who) - 1;
         rank = __shfl(r, src);
@@ -463,11 +412,11 @@ __global__ __launch_bounds__(256) void k_tg_mask(const float* __restrict__ grad,
         const int i = c0 + t;
         const unsigned u = (i < i1) ? __float_as_uint(grad[i]) : 0u;
         const bool tie = (i < i1) && u == kth;
-        const unsigned long long bt = __ballot(tie);
+        int before;
+        const unsigned long long bt = lk_ballot_rank(tie, lane, before);
         if (lane == 0) wa[w] = __popcll(bt);
         __syncthreads();
-        int tie_rank = (int)s_before + s_seen + __popcll(bt & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; ++q) tie_rank += wa[q];
+        const int tie_rank = lk_waves_before(wa, w, (int)s_before + s_seen + before);
         bool member = (i < i1) && (u > kth || (tie && tie_rank < ties_needed));
         if (member) {
             const int y = i / W, x = i - y * W;

@@ -4,28 +4,29 @@
 // REG = true (n <= LK_MASK_REG_MAX): the values stay in registers between the passes; otherwise they are re-read from
 // `scratch`.  The top byte of a depth takes a handful of values, so in the first pass the histogram is built with
 // one LDS add per (wave, distinct byte) instead of one same-address add per ray.
+// (the select itself, its histogram add and the shared-memory block: lk_scan_dev.h)
 #pragma once
 #include "lk_common.h"
+#include "lk_scan_dev.h"
 
 #define LK_MASK_REG_MAX 8192
 #define LK_MASK_VPT (LK_MASK_REG_MAX / 1024)
 // the batch-assembly kernel of the per-frame loops also comes in a 16-values-per-thread form (k_pregather<16>: the 10 000-ray mapping
 // batches of the TUM / ScanNet configs)
 #define LK_LOOP_MAX_R 16384
-struct LkMaskShared { unsigned hist[256]; unsigned s_prefix, s_rank, s_cnt, s_maxbits; };
 
 // u[q] = bit pattern of depth (t + 1024 q) if positive else 0 (REG) / scratch[i] likewise (!REG); mycnt / mymax = this
 // thread's count of positive depths and their largest bit pattern.  Returns thr; *any = false if no depth is positive.
 template <bool REG, int VPT = LK_MASK_VPT>
 __device__ __forceinline__ float lk_inside_thr(const unsigned (&u)[VPT], const uint32_t* __restrict__ scratch, int n,
-                                               unsigned mycnt, unsigned mymax, LkMaskShared& S, bool* any) {
+                                               unsigned mycnt, unsigned mymax, LkSelectShared& S, bool* any) {       // S.s_aux: the largest bit pattern
     const int t = threadIdx.x, lane = t & 63;
-    if (t == 0) { S.s_cnt = 0; S.s_maxbits = 0; }
+    if (t == 0) { S.s_cnt = 0; S.s_aux = 0; }
     __syncthreads();
     // one LDS atomic per WAVE (1024 same-address atomics cost microseconds)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { mycnt += __shfl_xor(mycnt, o); mymax = max(mymax, (unsigned)__shfl_xor((int)mymax, o)); }
-    if (lane == 0) { atomicAdd(&S.s_cnt, mycnt); atomicMax(&S.s_maxbits, mymax); }
+    if (lane == 0) { atomicAdd(&S.s_cnt, mycnt); atomicMax(&S.s_aux, mymax); }
     __syncthreads();
     const unsigned m = S.s_cnt;
     *any = m != 0;
@@ -33,7 +34,7 @@ __device__ __forceinline__ float lk_inside_thr(const unsigned (&u)[VPT], const u
     // Shortcut: thr = min(10*median, 1.2*max) is 1.2*max unless the median itself satisfies fl(10 v) < fl(1.2 max); that
     // predicate is monotone in v, so the (lower) median at rank (m-1)/2 satisfies it iff MORE than (m-1)/2 values do -
     // one counting pass instead of the 4-pass radix select (depth images: median ~ max/2, the select almost never runs).
-    const float mx12 = __fmul_rn(1.2f, __uint_as_float(S.s_maxbits));
+    const float mx12 = __fmul_rn(1.2f, __uint_as_float(S.s_aux));
     {
         unsigned below = 0;
         if (REG) {
@@ -51,59 +52,21 @@ __device__ __forceinline__ float lk_inside_thr(const unsigned (&u)[VPT], const u
     }
     const bool need_median = S.s_rank > (m - 1) / 2;                    // block-uniform
     __syncthreads();
-    if (t == 0) { S.s_prefix = 0; S.s_rank = (m - 1) / 2; }              // torch.median: lower of the two middle values
-    __syncthreads();
-    for (int shift = 24; need_median && shift >= 0; shift -= 8) {
-        if (t < 256) S.hist[t] = 0;
-        __syncthreads();
-        const unsigned prefix = S.s_prefix;
-        const unsigned himask = (shift == 24) ? 0u : (0xffffffffu << (shift + 8));
+    // torch.median: the lower of the two middle values
+    LK_RADIX_SELECT(S, t, (m - 1) / 2, need_median, if (t < 256) S.hist[t] = 0,
         if (REG) {
-#pragma unroll
-            for (int q = 0; q < VPT; ++q) {
+            _Pragma("unroll") for (int q = 0; q < VPT; ++q) {
                 const bool on = u[q] && (u[q] & himask) == prefix;
                 const unsigned digit = (u[q] >> shift) & 255u;
-                if (shift == 24) {      // all lanes walk the loop together (wave-uniform trip count)
-                    unsigned long long pending = __ballot(on);
-                    while (pending) {
-                        const int leader = __ffsll((long long)pending) - 1;
-                        const unsigned dl = __shfl(digit, leader);
-                        const unsigned long long same = __ballot(on && digit == dl);
-                        if (lane == leader) atomicAdd(&S.hist[dl], (unsigned)__popcll(same));
-                        pending &= ~same;
-                    }
-                } else if (on) {
-                    atomicAdd(&S.hist[digit], 1u);
-                }
+                if (shift == 24) LK_HIST_ADD_WAVE(S.hist, on, digit, lane)       // all lanes: the loop over q is wave-uniform
+                else if (on) atomicAdd(&S.hist[digit], 1u);
             }
         } else {
             for (int i = t; i < n; i += 1024) {
                 const unsigned v = scratch[i];
                 if (v && (v & himask) == prefix) atomicAdd(&S.hist[(v >> shift) & 255u], 1u);
             }
-        }
-        __syncthreads();
-        // locate the bin that holds the wanted rank: wave 0 scans the 256-bin histogram (4 bins per lane)
-        if (t < 64) {
-            const unsigned rank = S.s_rank;                   // every lane reads before the (later) single write
-            const unsigned h0 = S.hist[4 * t], h1 = S.hist[4 * t + 1], h2 = S.hist[4 * t + 2], h3 = S.hist[4 * t + 3];
-            const unsigned tot = h0 + h1 + h2 + h3;
-            unsigned incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned nbv = __shfl_up(incl, o);
-                if (t >= o) incl += nbv;
-            }
-            const unsigned excl = incl - tot;
-            if (rank >= excl && rank < incl) {              // exactly one lane
-                unsigned r = rank - excl, b = 4 * t;
-                if (r >= h0) { r -= h0; ++b; if (r >= h1) { r -= h1; ++b; if (r >= h2) { r -= h2; ++b; } } }
-                S.s_rank = r;
-                S.s_prefix = prefix | (b << shift);
-            }
-        }
-        __syncthreads();
-    }
+        })
     const float med = __uint_as_float(S.s_prefix);
     return need_median ? fminf(__fmul_rn(10.0f, med), mx12) : mx12;
 }
@@ -115,10 +78,9 @@ __device__ __forceinline__ float lk_inside_thr(const unsigned (&u)[VPT], const u
 // over the bit patterns (non-negative floats order as unsigned integers), values re-read from memory in every pass.
 // torch.median: the LOWER of the two middle values (rank (m - 1) / 2), NaN if any element is NaN (the mask is then empty).
 // No present ray: 0 (empty mask).
-struct LkMedianShared { unsigned hist[256]; unsigned s_prefix, s_rank, s_cnt, s_nan; };
-__device__ __forceinline__ float lk_block_median10(const float* __restrict__ resid, int n, LkMedianShared& S) {
+__device__ __forceinline__ float lk_block_median10(const float* __restrict__ resid, int n, LkSelectShared& S) {      // S.s_aux: NaN count
     const int t = threadIdx.x, lane = t & 63, nt = blockDim.x;
-    if (t == 0) { S.s_cnt = 0; S.s_nan = 0; }
+    if (t == 0) { S.s_cnt = 0; S.s_aux = 0; }
     __syncthreads();
     unsigned cnt = 0, nan = 0;
     for (int i = t; i < n; i += nt) {
@@ -127,53 +89,19 @@ __device__ __forceinline__ float lk_block_median10(const float* __restrict__ res
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); nan += __shfl_xor(nan, o); }
-    if (lane == 0) { atomicAdd(&S.s_cnt, cnt); atomicAdd(&S.s_nan, nan); }
+    if (lane == 0) { atomicAdd(&S.s_cnt, cnt); atomicAdd(&S.s_aux, nan); }
     __syncthreads();
     const unsigned m = S.s_cnt;
     if (m == 0) return 0.0f;
-    if (S.s_nan != 0) return __uint_as_float(0x7fc00000u);
+    if (S.s_aux != 0) return __uint_as_float(0x7fc00000u);
     __syncthreads();
-    if (t == 0) { S.s_prefix = 0; S.s_rank = (m - 1) / 2; }
-    __syncthreads();
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int b = t; b < 256; b += nt) S.hist[b] = 0;
-        __syncthreads();
-        const unsigned prefix = S.s_prefix;
-        const unsigned himask = (shift == 24) ? 0u : (0xffffffffu << (shift + 8));
+    // every pass aggregates: residuals share their top bytes, same-address adds would serialise
+    LK_RADIX_SELECT(S, t, (m - 1) / 2, true, for (int b = t; b < 256; b += nt) S.hist[b] = 0,
         for (int i0 = 0; i0 < n; i0 += nt) {         // workgroup-uniform trip count: every lane takes part in the ballots
             const unsigned v = (i0 + t < n) ? __float_as_uint(resid[i0 + t]) : 0x80000000u;
             const bool on = !(v & 0x80000000u) && (v & himask) == prefix;
             const unsigned digit = (v >> shift) & 255u;
-            // one LDS add per (wave, distinct digit): residuals share their top bytes, same-address adds would serialise
-            unsigned long long pending = __ballot(on);
-            while (pending) {
-                const int leader = __ffsll((long long)pending) - 1;
-                const unsigned dl = __shfl(digit, leader);
-                const unsigned long long same = __ballot(on && digit == dl);
-                if (lane == leader) atomicAdd(&S.hist[dl], (unsigned)__popcll(same));
-                pending &= ~same;
-            }
-        }
-        __syncthreads();
-        if (t < 64) {
-            const unsigned rank = S.s_rank;
-            const unsigned h0 = S.hist[4 * t], h1 = S.hist[4 * t + 1], h2 = S.hist[4 * t + 2], h3 = S.hist[4 * t + 3];
-            const unsigned tot = h0 + h1 + h2 + h3;
-            unsigned incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned nbv = __shfl_up(incl, o);
-                if (t >= o) incl += nbv;
-            }
-            const unsigned excl = incl - tot;
-            if (rank >= excl && rank < incl) {
-                unsigned r = rank - excl, b = 4 * t;
-                if (r >= h0) { r -= h0; ++b; if (r >= h1) { r -= h1; ++b; if (r >= h2) { r -= h2; ++b; } } }
-                S.s_rank = r;
-                S.s_prefix = prefix | (b << shift);
-            }
-        }
-        __syncthreads();
-    }
+            LK_HIST_ADD_WAVE(S.hist, on, digit, lane)
+        })
     return __fmul_rn(10.0f, __uint_as_float(S.s_prefix));
 }

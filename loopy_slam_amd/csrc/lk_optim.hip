@@ -5,6 +5,7 @@
 //   inside-mask threshold (median / max) and stable ballot + prefix-sum compaction
 //   (Tracker.py:153-160, Mapper.py:674-681, common.py:249-255).
 #include "lk_common.h"
+#include "lk_kernels.h"
 #include "lk_mask_dev.h"
 #include "lk_adam_dev.h"
 #include "lk_exposure_dev.h"
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void k_loss_tracker_pass1(int R, const float* 
 }
 
 __global__ __launch_bounds__(1024) void k_loss_tracker_median(int R, float* __restrict__ scratch) {
-    __shared__ LkMedianShared S;
+    __shared__ LkSelectShared S;
     const float thr = lk_block_median10(scratch, R, S);
     if (threadIdx.x == 0) scratch[R] = thr;
 }
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(1024) void k_loss_tracker_1wg(int R, const float* _
                                                            float* __restrict__ d_depth, float* __restrict__ d_color,
                                                            float* __restrict__ out, float* __restrict__ scratch) {
     __shared__ float sh[16];
-    __shared__ LkMedianShared S;
+    __shared__ LkSelectShared S;
     constexpr int VPT = LK_LOSS_1WG_MAX / 1024;
     float tm[VPT];
     float tsum = 0.0f, csum = 0.0f;
@@ -254,12 +255,11 @@ __global__ __launch_bounds__(1024) void k_compact(const uint8_t* __restrict__ ma
     for (int c0 = 0; c0 < n; c0 += 1024) {
         const int i = c0 + t;
         const bool keep = (i < n) && mask[i] != 0;
-        const unsigned long long b = __ballot(keep);
-        const int before = __popcll(b & ((1ull << lane) - 1ull));
+        int before;
+        const unsigned long long b = lk_ballot_rank(keep, lane, before);
         if (lane == 0) wcount[w] = __popcll(b);
         __syncthreads();
-        int woff = base;
-        for (int q = 0; q < w; ++q) woff += wcount[q];
+        const int woff = lk_waves_before(wcount, w, base);
         if (keep) out_index[woff + before] = i;
         __syncthreads();
         if (t == 1023) base = woff + __popcll(b);
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(1024) void k_compact(const uint8_t* __restrict__ ma
 template <bool REG>
 __global__ __launch_bounds__(1024) void k_inside_mask(const float* depth, int n, uint8_t* __restrict__ mask, float* depth_filtered,
                                                       float* __restrict__ out_thr, uint32_t* __restrict__ scratch) {
-    __shared__ LkMaskShared S;
+    __shared__ LkSelectShared S;
     constexpr int VPT = LK_MASK_VPT;
     const int t = threadIdx.x;
     unsigned u[VPT];
@@ -741,46 +741,23 @@ __global__ __launch_bounds__(256) void k_compact_count(const uint8_t* __restrict
     __syncthreads();
     if (threadIdx.x == 0) block_count[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
-__global__ __launch_bounds__(1024) void k_compact_scan(int32_t* __restrict__ block_count, int nb, int32_t* __restrict__ out_count) {
-    __shared__ int wsum[16];
-    __shared__ int carry;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nb; c0 += 1024) {
-        const int i = c0 + t;
-        const int v = (i < nb) ? block_count[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int nv = __shfl_up(incl, o); if (lane >= o) incl += nv; }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int base = carry;
-        for (int q = 0; q < w; ++q) base += wsum[q];
-        if (i < nb) block_count[i] = base + incl - v;           // exclusive offset of block i
-        __syncthreads();
-        if (t == 1023) carry = base + incl;
-        __syncthreads();
-    }
-    if (t == 0) *out_count = carry;
-}
 __global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t* __restrict__ mask, int n, const int32_t* __restrict__ block_off,
                                                          int32_t* __restrict__ out_index) {
     __shared__ int wc[4];
     const int i = blockIdx.x * 256 + (int)threadIdx.x, lane = lk_lane(), w = (int)threadIdx.x >> 6;
     const bool keep = i < n && mask[i] != 0;
-    const unsigned long long b = __ballot(keep);
+    int before;
+    const unsigned long long b = lk_ballot_rank(keep, lane, before);
     if (lane == 0) wc[w] = __popcll(b);
     __syncthreads();
-    int off = block_off[blockIdx.x];
-    for (int q = 0; q < w; ++q) off += wc[q];
-    if (keep) out_index[off + __popcll(b & ((1ull << lane) - 1ull))] = i;
+    const int off = lk_waves_before(wc, w, block_off[blockIdx.x]);
+    if (keep) out_index[off + (unsigned)before] = i;
 }
 
 int lk_launch_compact_mb(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, hipStream_t st) {
     const int nb = lk_cdiv(n, 256);
     hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(256), 0, st, mask, n, block_scratch);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, block_scratch, nb, out_count);
+    lk_launch_carry_scan_total(block_scratch, nb, out_count, st);
     hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(256), 0, st, mask, n, (const int32_t*)block_scratch, out_index);
     return LK_OK;
 }
@@ -789,11 +766,15 @@ int lk_launch_compact(const uint8_t* mask, int n, int32_t* out_index, int32_t* o
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, mask, n, out_index, out_count);
     return LK_OK;
 }
+int lk_launch_compact_any(const uint8_t* mask, int n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, hipStream_t st) {
+    return n <= LK_COMPACT_ONE_BLOCK_MAX ? lk_launch_compact(mask, n, out_index, out_count, st)
+                                         : lk_launch_compact_mb(mask, n, out_index, out_count, block_scratch, st);
+}
 
 extern "C" int lk_compact(const uint8_t* mask, int32_t n, int32_t* out_index, int32_t* out_count, void* stream_) {
     LK_REQUIRE(n >= 0 && out_count, "lk_compact: bad arguments");
     LK_REQUIRE(n == 0 || (mask && out_index), "lk_compact: NULL buffer");
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, (hipStream_t)stream_, mask, (int)n, out_index, out_count);
+    lk_launch_compact(mask, (int)n, out_index, out_count, (hipStream_t)stream_);
     LK_LAUNCH_CHECK();
     return LK_OK;
 }
@@ -835,8 +816,7 @@ extern "C" int lk_knn_flag_rows(lk_knn_t knn, const uint8_t* flags, int64_t n, v
 extern "C" int lk_compact_large(const uint8_t* mask, int32_t n, int32_t* out_index, int32_t* out_count, int32_t* block_scratch, void* stream_) {
     LK_REQUIRE(n >= 0 && out_count, "lk_compact_large: bad arguments");
     LK_REQUIRE(n == 0 || (mask && out_index && block_scratch), "lk_compact_large: NULL buffer");
-    if (n <= 16384) lk_launch_compact(mask, n, out_index, out_count, (hipStream_t)stream_);
-    else lk_launch_compact_mb(mask, n, out_index, out_count, block_scratch, (hipStream_t)stream_);
+    lk_launch_compact_any(mask, n, out_index, out_count, block_scratch, (hipStream_t)stream_);
     LK_LAUNCH_CHECK();
     return LK_OK;
 }

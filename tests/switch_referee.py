@@ -9,8 +9,8 @@ from loopy_slam_amd import _ffi
 
 # ---------------------------------------------------------------------------- the switches
 MASK_REG_MAX = 8192             # lk_mask_dev.h: #define LK_MASK_REG_MAX 8192 (lk_inside_mask: registers / scratch; k_pregather<8> / <16>)
-COMPACT_ONE_BLOCK_MAX = 16384   # lk_optim.hip::lk_compact_large: `if (n <= 16384)` one workgroup, else count / scan / scatter
-COMPACT_PASS = 1024             # k_compact: 1024 elements per pass; k_compact_scan: 1024 block counts per pass (= 262 144 elements)
+COMPACT_ONE_BLOCK_MAX = 16384   # lk_kernels.h: #define LK_COMPACT_ONE_BLOCK_MAX 16384 (lk_launch_compact_any: one workgroup up to it, else count / scan / scatter)
+COMPACT_PASS = 1024             # k_compact: 1024 elements per pass; k_carry_scan<1024, 1, true>: 1024 block counts per pass (= 262 144 elements)
 COMPACT_BLOCK = 256             # k_compact_count / k_compact_scatter: elements per block, one int of block_scratch each
 GRID_CAP_ROWS = 4096            # lk_touch_rows / lk_knn_flag_rows: `if (gx > 4096) gx = 4096`, 256 threads: grid-stride above 1 048 576
 GRID_CAP_BUCKET = 1024          # lk_bucket_copy: `if (gx > 1024) gx = 1024`, 256 threads: grid-stride above 262 144 floats per segment

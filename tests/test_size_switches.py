@@ -45,6 +45,7 @@ def test_sizes_mirror_the_sources():
     assert define(src('lk_mask_dev.h'), 'LK_MASK_REG_MAX') == sw.MASK_REG_MAX
     assert define(src('lk_sample.hip'), 'LK_T16_MAX_P') == sw.T16_MAX_P
     assert define(src('lk_kernels.h'), 'LK_DEEP_MAX_TILES') == define(src('lk_kernels.h'), 'LK_DEEP_MAX_TILES_FWD') == sw.DEEP_MAX_TILES
+    assert define(src('lk_kernels.h'), 'LK_COMPACT_ONE_BLOCK_MAX') == sw.COMPACT_ONE_BLOCK_MAX
     header = src(os.path.join('..', '..', 'include', 'loopy_hip.h'))
     assert define(header, 'LK_EXPOSURE_MAX_F') == sw.EXPOSURE_MAX_F and define(header, 'LK_ADAM_MAX_SEG') == sw.ADAM_MAX_SEG
 

@@ -23,7 +23,7 @@ ALGO = {'color': (5000, 31.6e3), 'geo': (5000, 0.5 * 31.6e3), 'track': (1500, 11
 # kernels of the workload's SET-UP (synthetic scene, map insertion, index build - once per process, torch's own element-wise kernels): not
 # part of an iteration; listed in one line under the table
 SETUP = {'k_aabb', 'k_count', 'k_scatter', 'k_zero_counts', 'k_grid_finalize', 'k_add_test', 'k_add_emit', 'k_compact', 'k_frustum_sample', 'k_frustum_mask',
-         'k_compact_count', 'k_compact_scan', 'k_compact_write'}
+         'k_compact_count', 'k_carry_scan<1024, 1, true>', 'k_compact_write'}
 
 
 def short(n):
