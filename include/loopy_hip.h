@@ -744,6 +744,69 @@ int lk_img_eval_ws_bytes(int32_t H, int32_t W, int64_t* out_bytes);
 int lk_img_eval(const float* gt_color, const float* color /*[H][W][3], values in [0, 1]*/, const float* gt_depth, const float* depth /*[H][W]*/,
                 int32_t H, int32_t W, int32_t with_msssim, void* ws, double* out_rec /*device, [LK_IMG_REC]*/, void* stream);
 
+/* ---------------------------------------------------------------- place recognition
+ * Which earlier segment does the newest keyframe look at?  The reference answers with OpenCV's ORB and a DBoW3 vocabulary tree
+ * (src/neural_point.py:126-142, 619-644, 1076-1107); neither can be assumed, so the contract below is this library's own: an ORB-like binary
+ * descriptor and a direct descriptor-matching score.  INTEGER ARITHMETIC FROM THE GREY IMAGE ONWARD: the kernels, the host emulator and the
+ * referee (tests/place_referee.py) agree bit for bit.  No floating-point atomic; equal inputs give equal bits.
+ *
+ * Grey image.  color[H][W][3] fp32.  Per channel q = clamp((int)fmaf(c, 255.0f, 0.5f), 0, 255) - one fused multiply-add, truncated; a NaN gives 0 -
+ * and grey = (1868 q_0 + 9617 q_1 + 4899 q_2 + 8192) >> 14.  Channel 0 takes the BLUE weight: the reference hands its RGB image to
+ * cv2.COLOR_BGR2GRAY, and that is kept.
+ * Pyramid.  n_levels levels (<= LK_PLACE_MAX_LEVELS), ratio 6/5: a level of n pixels along a side is followed by one of floor(5 n / 6).  Output
+ * pixel i samples source coordinate (12 i + 1) / 10 per axis: t = 12 i + 1, i0 = min(t / 10, n - 1), i1 = min(i0 + 1, n - 1), f = t % 10, weights
+ * (10 - f, f) in tenths; value = (sum over the four pixels of wy wx v + 50) / 100.  A level whose interior is empty after the
+ * LK_PLACE_BORDER-pixel border has no keypoints and is no error.  Pixel i of level l sits at off[l] + i of every per-pixel array of the
+ * workspace (levels one after another, rows of w[l] pixels).
+ * Corners, per level, at the pixels with LK_PLACE_BORDER <= x < w - LK_PLACE_BORDER and the same in y.  FAST-9: with p the pixel and the
+ * 16-pixel circle of radius 3 - (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3) as
+ * (dx, dy) - a corner has 9 consecutive circle pixels (cyclically) all > p + 20 or all < p - 20.  Score: with the 3 x 3 Sobel derivatives
+ * Ix = (v(x+1,y-1) + 2 v(x+1,y) + v(x+1,y+1)) - (the same at x-1), Iy = (v(x-1,y+1) + 2 v(x,y+1) + v(x+1,y+1)) - (the same at y-1) and
+ * a = sum Ix^2, b = sum Ix Iy, c = sum Iy^2 over the 7 x 7 block centred on the corner: R = 25 (a c - b^2) - (a + c)^2 in int64, Harris with
+ * k = 0.04 exactly.  A corner is a KEY if none of its 8 neighbours is a corner that precedes it in the total order (R descending, flat pixel
+ * index ascending).
+ * Selection (host).  Level l keeps its first quota[l] keys in that order: d_0 = n_features (1 - f) / (1 - f^n_levels), f = 5/6, d_{l+1} = d_l f
+ * in fp64; quota[l] = floor(d_l + 0.5) for l < n_levels - 1 and the last level gets max(n_features - the sum of the others, 0) (ORB's rule).
+ * Unused quota is not redistributed.  Output order: level ascending, then rank.
+ * Orientation.  m10 = sum dx v, m01 = sum dy v over the level's grey pixels with dx^2 + dy^2 <= 225; the bin is the k in [0, LK_PLACE_BINS)
+ * that maximises m10 C[k] + m01 S[k] (int64), lowest k on a tie, with C[k], S[k] = rint(2^14 cos / sin(12 degrees k)) as int32 - cos_sin[2][30],
+ * the caller's.  No atan2.
+ * Descriptor.  S = the level's grey image under the separable binomial [1 6 15 20 15 6 1] along x and then y, edge-clamped, kept as the
+ * undivided uint32 sum.  Bit i of 256 = S(p + a_i) < S(p + b_i), word i / 32, position i % 32; (a_i, b_i) = pattern[bin][i] = (ax, ay, bx, by) int8.
+ * The base pattern (bin 0): coordinate c = 0 .. 3 of test i is (u0 % 7) + (u1 % 7) + (u2 % 7) + (u3 % 7) - 12 with (u0 .. u3) = Philox4x32-10, key
+ * (LK_PLACE_SEED, 0), counter (i, c, 0, 0) (the rounds are written out at lk_ransac_hypotheses).  Bin k: (x', y') = (rint(c x - s y),
+ * rint(s x + c y)) with c, s = cos, sin of 12 degrees k in fp64, rounded once on the host (loopy_slam_amd/place.py: pattern_tables).  All
+ * coordinates stay within 17 pixels, the disc within 15: inside the border.
+ *
+ * lk_place_ws_bytes: out_layout[8] = workspace bytes, total pixels P = off[n_levels], and the byte offsets of grey (uint8 [P]), S (uint32 [P]),
+ * the scores (int64 [P], INT64_MIN for a pixel that is no corner), the key list (int32 [P]: flat pixels of the keys, ascending), its length (int32)
+ * and the key mask (uint8 [P]).  The workspace is 8-byte aligned; its contents on entry do not matter.  H W <= LK_PLACE_MAX_PIXELS.
+ * lk_place_detect: everything up to the key list, and out_level_counts[n_levels] (device) = the keys of each level.  The caller reads those back
+ * - the one synchronisation of an image -, orders each level's keys by their scores (a stable sort of the negated scores: the list is ascending
+ * in the pixel index already) and passes the chosen flat pixels as sel[N] to
+ * lk_place_describe: out_kp[N][4] = (x, y, level, bin) in the level's own pixel grid, out_desc[N][8].  A pixel outside a level's border region is
+ * not a keypoint of this library: its descriptor is zero.
+ *
+ * lk_place_match_score: query[n_query][8] against the segments db[S][F][8] of which the first counts[s] rows are in use (n_query <= F), both
+ * directions in one launch: rows[S][2][F][3] int32 = (best, second, index) - direction 0 for every query row over the segment's rows, direction 1
+ * for every row of the segment over the query rows.  best = the smallest Hamming distance, index = the lowest row that has it, second = the
+ * smallest distance among the OTHER rows; LK_PLACE_NO_MATCH (257) where there is none (and index -1).  Rows beyond a set's size are not
+ * written.  out_count[s] = the query rows i with index j >= 0 whose row j of direction 1 has index i (mutual), best <= max_hamming and
+ * 5 best <= 4 second.  The caller's score is out_count / min(n_query, counts[s]), 0 if either is empty. */
+#define LK_PLACE_MAX_LEVELS 16
+#define LK_PLACE_MAX_PIXELS 16777216
+#define LK_PLACE_BORDER 20
+#define LK_PLACE_FAST_T 20
+#define LK_PLACE_BINS 30
+#define LK_PLACE_SEED 0x4F524221u
+#define LK_PLACE_NO_MATCH 257
+int lk_place_ws_bytes(int32_t H, int32_t W, int32_t n_levels, int64_t* out_layout /*[8]*/);
+int lk_place_detect(const float* color, int32_t H, int32_t W, int32_t n_levels, void* ws, int32_t* out_level_counts, void* stream);
+int lk_place_describe(const void* ws, int32_t H, int32_t W, int32_t n_levels, const int32_t* sel, int32_t N, const int32_t* cos_sin,
+                      const int8_t* pattern, int32_t* out_kp, uint32_t* out_desc, void* stream);
+int lk_place_match_score(const uint32_t* query, int32_t n_query, const uint32_t* db, const int32_t* counts, int32_t S, int32_t F,
+                         int32_t max_hamming, int32_t* rows, int32_t* out_count, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

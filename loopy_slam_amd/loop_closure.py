@@ -11,7 +11,10 @@ Reference                                                  here
   src/common.py  preprocess_point_cloud (voxel, FPFH)       fpfh_features -> lk_voxel_downsample, lk_normals, lk_fpfh
   src/common.py  execute_global_registration (RANSAC)      global_registration -> lk_feature_match, lk_ransac_hypotheses, lk_ransac_score
 
-Out of scope: place recognition (ORB + DBoW); which pairs are registered is `loop_closure.candidates` ('pose' or a callable).  The
+  src/neural_point.py  ORB + DBoW query, compute_dbow_score  LoopCloser.appearance_candidates / on_mapped_frame -> place.PlaceRecognizer
+
+Which pairs are registered is `loop_closure.candidates`: 'pose' (the tracked keyframe poses), 'appearance' (place recognition: the
+library's own binary descriptor and matching score, place.py - not OpenCV's ORB, not a DBoW vocabulary) or a callable.  The
 methods 'icp' and 'robust_icp' start from the tracked poses (the identity between two segments of one world frame: the reference's
 method == "icp" branch, plus the Tukey fine stage of its "robust_icp" branch); 'fpfh_robust_icp' puts the reference's global start in
 front of them - voxel downsample, FPFH, mutual feature matches, 3-point RANSAC, all on the device - and survives a loop that has really
@@ -24,7 +27,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _ffi, core
+from . import _ffi, core, place
 from ._ffi import ptr
 
 COARSE_DIST, FINE_DIST, TUKEY_K, NORMAL_RADIUS = 0.3, 0.03, 0.01, 0.1      # src/common.py:594-595, 607, 647
@@ -32,6 +35,7 @@ METHODS = ('identity', 'icp', 'robust_icp', 'fpfh_robust_icp')
 # the global start (src/common.py preprocess_point_cloud / execute_global_registration): voxel, normals over 2 voxels, features over 5,
 # checkers at 0.9 and 1.5 voxels, confidence and trial cap of the reference
 VOXEL, EDGE_RATIO, GLOBAL_CONF, GLOBAL_ITER, RANSAC_BATCH = 0.04, 0.9, 0.99999, 10_000_000, 65536
+MIN_SCORE = 0.223
 
 
 # ------------------------------------------------------------------------------------------------ SE(3), fp64, vectors (omega, v)
@@ -529,7 +533,11 @@ def optimize_pose_graph(n_nodes, edges, prune=0.25, lc_pref=5.0, max_dist=FINE_D
 
 # ------------------------------------------------------------------------------------------------ the closer
 DEFAULTS = {'enabled': False, 'method': 'robust_icp', 'candidates': 'pose', 'max_center_dist': 1.5, 'min_axis_cos': 0.5,
-            'global_conf': GLOBAL_CONF, 'global_iter': GLOBAL_ITER, 'global_seed': 0}      # the last three: 'fpfh_robust_icp' only
+            'global_conf': GLOBAL_CONF, 'global_iter': GLOBAL_ITER, 'global_seed': 0,      # these three: 'fpfh_robust_icp' only
+            # candidates 'appearance' only.  min_score: midway between the two figures of profiles/place_recognition.md (the highest score
+            # of two views 50 or more poses apart, the lowest of two within 5)
+            'min_score': MIN_SCORE, 'n_features': 500, 'n_levels': 8, 'max_hamming': 64}
+CANDIDATES = ('pose', 'appearance')
 
 
 def settings(cfg):
@@ -550,9 +558,18 @@ class LoopCloser:
                                       '(SURVEY.md 8(e)); that exchange is not built - run loop closure on one rank')
         if lc['method'] not in METHODS:
             raise NotImplementedError(f"loop_closure.method {lc['method']!r}: one of {METHODS}")
+        if not callable(lc['candidates']) and lc['candidates'] not in CANDIDATES:
+            raise NotImplementedError(f"loop_closure.candidates {lc['candidates']!r}: one of {CANDIDATES} or a callable")
         tr = cfg.get('tracking', {})
         self.cfg, self.npc, self.slam, self.eng = lc, npc, slam, npc.eng
         self.method, self.candidates = lc['method'], lc['candidates']
+        # place recognition (the reference's values: configs/point_slam.yaml): owned in the 'appearance' mode only
+        self.kval, self.dbow_filter, self.mult_dbow = int(tr.get('kval', 2)), bool(tr.get('dbow_filter', True)), float(tr.get('mult_dbow', 1.0))
+        self.min_score = float(lc['min_score'])
+        self.place = None
+        if lc['candidates'] == 'appearance':
+            self.place = place.PlaceRecognizer(self.eng, int(lc['n_features']), int(lc['n_levels']), int(lc['max_hamming']))
+        self.seg_desc, self.self_score, self.last_scores = [], [], None      # per segment: the keyframe's descriptors, compute_dbow_score's minimum
         self.global_cfg = {'conf': float(lc['global_conf']), 'max_iter': int(lc['global_iter']), 'seed': int(lc['global_seed'])}
         self.min_dist = tr.get('min_dist', 1)
         self.prune_pgo, self.lc_pref = tr.get('prune_pgo', 0.25), tr.get('lc_pref', 5.0)
@@ -588,6 +605,40 @@ class LoopCloser:
                 out.append((s, t))
         return out
 
+    # ---- place recognition
+    def describe_segments(self, segments):
+        """Every segment's keyframe is described once and joins the database, in segment order."""
+        for i in range(len(self.seg_desc), len(segments)):
+            _, desc = self.place.describe(segments[i]['color'])
+            self.place.add(desc)
+            self.seg_desc.append(desc)
+            self.self_score.append(-1.0)
+
+    def on_mapped_frame(self, color, segments):
+        """slam.Mapper: a mapped frame that opens no segment.  self_score[t] of the running segment t is the lowest score between its
+        keyframe and its other mapped frames (the reference's compute_dbow_score), -1 while it has none."""
+        if self.place is None or not segments:
+            return
+        self.describe_segments(segments)
+        t = len(segments) - 1
+        _, desc = self.place.describe(color)
+        sc = float(self.place.scores(desc)[t])
+        self.self_score[t] = sc if self.self_score[t] < 0 else min(self.self_score[t], sc)
+
+    def appearance_candidates(self, segments):
+        """Pairs (newest, t) by appearance: of the earlier segments with |s - t| > tracking.min_dist, score > loop_closure.min_score and -
+        tracking.dbow_filter - score > tracking.mult_dbow x self_score[t], the tracking.kval best (score descending, t ascending).
+        The reference thresholds with the QUERY segment's own score; the newest segment has no frames of its own yet, so the candidate's is
+        used (the score is symmetric up to the ratio test, which looks at the query's second-best match)."""
+        self.describe_segments(segments)
+        s = len(segments) - 1
+        scores = self.place.scores(self.seg_desc[s])
+        self.last_scores = scores
+        ok = [t for t in range(s) if abs(s - t) > self.min_dist and scores[t] > self.min_score and
+              (not self.dbow_filter or scores[t] > self.mult_dbow * self.self_score[t])]
+        ok.sort(key=lambda t: (-scores[t], t))
+        return [(s, t) for t in ok[:max(self.kval, 0)]]
+
     def filter_edges(self, regs):
         """The reference's old_trans_mag_filter branch: if the translation magnitudes of the successful loop registrations spread by no
         more than tracking.std_threshold all of them are kept; otherwise those below their trans_mag_percentile-th percentile with a
@@ -609,7 +660,10 @@ class LoopCloser:
         self.last_edges, self.last_result, self.last_registrations = None, None, []
         if n < 3:
             return None
-        pairs = self.candidates(segments) if callable(self.candidates) else self.pose_candidates(segments)
+        if callable(self.candidates):
+            pairs = self.candidates(segments)
+        else:
+            pairs = self.appearance_candidates(segments) if self.candidates == 'appearance' else self.pose_candidates(segments)
         pairs = [(int(s), int(t)) for s, t in pairs]
         if not pairs:
             return None
@@ -689,6 +743,8 @@ class LoopCloser:
         segments = mapper.segments
         self.current_segment = len(segments) - 1
         self.npc._seg[first_new_row:self.npc.n] = self.current_segment
+        if self.place is not None:
+            self.describe_segments(segments)
         pg = self.compute_correction(segments)
         if pg is None:
             return None

@@ -11,8 +11,8 @@ All arithmetic of the hot path runs in libloopyhip (loopy_slam_amd.core / .steps
 per-frame bookkeeping in torch.  Loop closure's geometric back end (segment registration, pose graph, map correction) is
 loop_closure.py, off by default (cfg['loop_closure']['enabled']); the final mesh (TSDF fusion of the mapped frames + marching
 cubes) is tsdf.py, off by default (cfg['meshing']['enabled']); the evaluation of the re-rendered frames and of the trajectory is
-render_eval.py, off by default (cfg['rendering_eval']['enabled']); place recognition stays out of scope, as do datasets and
-visualisation (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
+render_eval.py, off by default (cfg['rendering_eval']['enabled']); place recognition is place.py
+(loop_closure.candidates: 'appearance'); datasets and visualisation stay out of scope (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
 the default is the gfx950 library on the current CUDA device.
 """
 import math
@@ -783,6 +783,8 @@ class Mapper:
                                   'exposure_feat': self.cur_exposure_feat.detach() if self.slam.encode_exposure else None})
             if self.closer is not None and self.closer.on_new_segment(self, rows_before) is not None:
                 cur_c2w = self.segments[-1]['est_c2w'].clone()          # the corrected pose: the tracker starts the next frame from it
+        elif self.closer is not None and self.closer.place is not None:
+            self.closer.on_mapped_frame(gt_color, self.segments)        # place recognition: the segment's own score (compute_dbow_score)
         self.prev_c2w = cur_c2w.clone()         # Mapper.py:1001
         slam.mapping_idx[0] = idx
         return self.last_log

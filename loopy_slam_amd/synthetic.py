@@ -141,6 +141,23 @@ def furnished_color(points, obj):
     return torch.where((obj >= 0)[:, None], box, wall).clamp(0, 1).float()
 
 
+# 'textured' scene: the furnished room with its colour multiplied by 0.25 + 0.75 h, h in [0, 1] an integer hash of the 12-cm cell a surface
+# point lies in - random-brightness cells about a dozen pixels wide, the corners a place-recognition descriptor needs (FAST-9 at threshold 20
+# finds none in 'plain' and a few dozen in 'furnished').
+TEXTURE_CELL = 0.12
+
+
+def cell_brightness(points):
+    """h [R] in [0, 1]: a hash of floor((p + 1e-4) / TEXTURE_CELL) per axis (the offset keeps the axis-aligned faces off the cell boundaries)."""
+    c = torch.floor((points.double() + 1e-4) / TEXTURE_CELL).long()
+    v = (c[:, 0] * 73856093) ^ (c[:, 1] * 19349663) ^ (c[:, 2] * 83492791)
+    v = v & 0xFFFFFFFF
+    v = ((v ^ (v >> 16)) * 0x45D9F3B) & 0xFFFFFFFF
+    v = ((v ^ (v >> 16)) * 0x45D9F3B) & 0xFFFFFFFF
+    v = v ^ (v >> 16)
+    return ((v & 0xFFFF).double() / 65535.0).float()
+
+
 def render_frame(k, intr=TUM_INTR, holes=0.02, device='cpu', seed=1219, n_poses=200, motion='loop', scene='plain'):
     """Synthetic RGB-D frame k: (depth [H,W], color [H,W,3], c2w [4,4])."""
     H, W = intr['H'], intr['W']
@@ -148,9 +165,11 @@ def render_frame(k, intr=TUM_INTR, holes=0.02, device='cpu', seed=1219, n_poses=
     jj, ii = torch.meshgrid(torch.arange(H, device=device, dtype=torch.float32),
                             torch.arange(W, device=device, dtype=torch.float32), indexing='ij')
     ro, rd = pixel_rays(c2w, ii.reshape(-1), jj.reshape(-1), intr)
-    if scene == 'furnished':
+    if scene in ('furnished', 'textured'):
         d, obj = furnished_hit(ro, rd)
         col = furnished_color(ro + rd * d[:, None], obj)
+        if scene == 'textured':
+            col = col * (0.25 + 0.75 * cell_brightness(ro + rd * d[:, None]))[:, None]
     else:
         d = room_depth(ro, rd)
         col = room_color(ro + rd * d[:, None])
