@@ -832,6 +832,10 @@ int lk_debug_occupancy(int32_t out[5]);
  * microseconds (0 = off, the default) - a missing ordering between the side stream and the launch stream then fails deterministically
  * instead of by timing (tests/test_split_step_order.py).  Results must not depend on it. */
 int lk_debug_side_delay(int32_t us);
+/* Test hook: the fp16 two-piece cut of the forward kernels (hi = rtz_f16(x), lo = rtz_f16(x - hi)) over n values (n even, device
+ * pointers): hi / lo [n/2] = the packed pieces of the pairs (x[2i], x[2i+1]) in the production form, hi_ref / lo_ref [n/2] = the same
+ * from the convert-and-subtract form it replaced (tests/test_split_forms.py: the two must agree bit for bit). */
+int lk_debug_split_forms(const float* x, int32_t n, uint32_t* hi, uint32_t* lo, uint32_t* hi_ref, uint32_t* lo_ref, void* stream);
 
 #ifdef __cplusplus
 }

@@ -408,6 +408,33 @@ extern "C" int lk_debug_occupancy(int32_t out[5]) {
     out[3] = lk_occupancy_relpos_bwd_fused(); out[4] = lk_occupancy_wgrad();
     return LK_OK;
 }
+// Test hook (tests/test_split_forms.py): the fp16 two-piece cut of the forward kernels over an array.  FMA = the production form
+// (lk_cut2h: remainder by one v_fma_mix_f32), !FMA = the form it replaced, convert the high piece back and subtract - kept here,
+// and only here, as the reference the production form has to equal bit for bit.
+template <bool FMA>
+__global__ void k_split_forms(const float* __restrict__ x, int n2, unsigned* __restrict__ hi, unsigned* __restrict__ lo) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n2) return;
+    const float a = x[2 * i], b = x[2 * i + 1];
+    unsigned h, l;
+    if (FMA) lk_cut2h(a, b, h, l);
+    else {
+        const lk_f16x2 hh = __builtin_amdgcn_cvt_pkrtz(a, b);
+        const lk_f16x2 ll = __builtin_amdgcn_cvt_pkrtz(a - (float)hh[0], b - (float)hh[1]);
+        h = __builtin_bit_cast(unsigned, hh); l = __builtin_bit_cast(unsigned, ll);
+    }
+    hi[i] = h; lo[i] = l;
+}
+extern "C" int lk_debug_split_forms(const float* x, int32_t n, uint32_t* hi, uint32_t* lo, uint32_t* hi_ref, uint32_t* lo_ref, void* stream) {
+    LK_REQUIRE(x && hi && lo && hi_ref && lo_ref, "lk_debug_split_forms: null pointer");
+    LK_REQUIRE(n > 0 && n % 2 == 0, "lk_debug_split_forms: n must be positive and even");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_split_forms<true>, dim3(lk_cdiv(n / 2, 256)), dim3(256), 0, st, x, n / 2, hi, lo);
+    LK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_split_forms<false>, dim3(lk_cdiv(n / 2, 256)), dim3(256), 0, st, x, n / 2, hi_ref, lo_ref);
+    LK_LAUNCH_CHECK();
+    return LK_OK;
+}
 bool lk_serial_mode() { if (g_serial < 0) g_serial = getenv("LK_SERIAL") != nullptr ? 1 : 0; return g_serial != 0; }
 LkAuxStream& lk_aux_stream() {
     static LkAuxStream s, none;

@@ -81,10 +81,10 @@ __device__ __forceinline__ BwdSample bwd_sample(const LkDecodeBwdArgs& a, int ti
 // DEEP: as in the forward (lk_decode.hip) - launches whose tiles are all resident at once fetch more blocks of W_i^T ahead
 // (all eight; the register count of the kernel is set by its geometry role)
 // TL: the launch may belong to the tracking loop (LkDecodeBwdArgs::tl_n_part) - d raw formed in the prologue instead of read
-template <bool H16, bool DEEP, bool TL>
+template <bool H16, bool DEEP, bool TL, bool SA = false>
 __device__ __forceinline__ void decode_bwd_col_wg(const LkDecodeBwdArgs& a, int tile, int w, int lane,
                                                   u32x4* __restrict__ s_x /* [2][24*64] */, float (*s_o)[3 * 32]) {
-    typedef BwdPiece<H16> PC;
+    typedef BwdPiece<H16, SA> PC;
     typedef typename PC::T Piece;
     constexpr int NP = PC::NP;
     // (a.dscale: a power of two from the device, exact in both directions)
@@ -312,11 +312,11 @@ __device__ __forceinline__ void decode_bwd_col_wg(const LkDecodeBwdArgs& a, int 
 // tile alive; the loop is not unrolled - three copies of the 48 cosines and 144 reductions are code nobody needs):
 // e_u = sin(x_u): ge_u = de_u cos(x_u);  WW: dB[i][u] += sum_s ge_u a_i(s) (-> part);  WP: dp_i += ge_u 2 pi B[i][u]
 // GH16: the pieces are fp16 pairs of the 2^10-scaled chain (decode_bwd_geo_wave); isc scales d e back
-template <bool WP, bool WW, bool GH16>
+template <bool WP, bool WW, bool GH16, bool SA = false>
 __device__ __forceinline__ void geo_embed_bwd(const u32x4* __restrict__ FB, const float* __restrict__ B, const u32x4* __restrict__ park,
-                                              const typename BwdPiece<GH16>::T (&y0)[2], float isc, float a0, float a1, float a2,
+                                              const typename BwdPiece<GH16, SA>::T (&y0)[2], float isc, float a0, float a1, float a2,
                                               float& dpx, float& dpy, float& dpz, float* __restrict__ part, int lane) {
-    typedef BwdPiece<GH16> PC;
+    typedef BwdPiece<GH16, SA> PC;
     constexpr int NP = PC::NP;
     const int h = lane >> 5;
 #pragma unroll 1
@@ -363,9 +363,9 @@ __device__ __forceinline__ void geo_embed_bwd(const u32x4* __restrict__ FB, cons
 // gradients (LK_FLAG_UNIT_LOSS_GRADS without ray gradients), so d occ = d depth . d depth / d occ + d colour . d colour / d occ is at most
 // of the order of the sample spacing.  The chain is linear in d occ: d occ is multiplied by 2^10 once, d c and d e are scaled back where
 // they leave the chain.  Half the matrix instructions of the wave's dependent chain (three per product instead of six).
-template <bool GH16>
+template <bool GH16, bool SA = false>
 __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, int tile, float* __restrict__ part, u32x4* __restrict__ park) {
-    typedef BwdPiece<GH16> PC;
+    typedef BwdPiece<GH16, SA> PC;
     typedef typename PC::T Piece;
     constexpr int NP = PC::NP;
     constexpr float SC = GH16 ? 1024.0f : 1.0f, ISC = GH16 ? 1.0f / 1024.0f : 1.0f;
@@ -461,9 +461,9 @@ __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, in
         const Piece y0[2] = {PC::split(dy, 0), PC::split(dy, 1)};
         // (the flags select the form once, outside the loop: with `if (want_p)` per value the compiler sinks the whole d p chain - and with it
         // all 48 ge values and the 144 entries of B they need - to the end of the kernel: 216 registers instead of ~130)
-        if (want_p && !want_w) geo_embed_bwd<true, false, GH16>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
-        else if (want_w && !want_p) geo_embed_bwd<false, true, GH16>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
-        else geo_embed_bwd<true, true, GH16>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
+        if (want_p && !want_w) geo_embed_bwd<true, false, GH16, SA>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
+        else if (want_w && !want_p) geo_embed_bwd<false, true, GH16, SA>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
+        else geo_embed_bwd<true, true, GH16, SA>(FB, W + G_EB, park, y0, ISC, a0, a1, a2, dpx, dpy, dpz, part, lane);
     }
     if (want_p) {
         dpx += __shfl_xor(dpx, 32); dpy += __shfl_xor(dpy, 32); dpz += __shfl_xor(dpz, 32);
@@ -485,6 +485,9 @@ __global__ __launch_bounds__(256, LK_DBWD_MINB) void k_decode_bwd(LkDecodeBwdArg
     __shared__ u32x4 s_x[2 * 24 * 64];
     __shared__ float s_o[4][3 * 32];
     const int w = (int)threadIdx.x >> 6;
+    // scalar-base fragment loads (lk_common.h: lk_sbase) in every form but the mapper's <true, false, true>: with them it takes 175 registers
+    // instead of 167 - two workgroups per compute unit, not three - for no fewer vector instructions (profiles/valu_diet.md)
+    constexpr bool SA = (LK_FRAG_SADDR != 0) && !(H16 && !DEEP && GH16);
     LK_STAMP(0);
     const int P_live = a.live_rays ? min(a.P, *a.live_rays * a.S) : a.P;       // as k_decode_fwd
     // geometry workgroups FIRST in the grid: a geometry tile is one wave's 20-us chain - dispatched behind the colour tiles (as in rounds 1-2)
@@ -496,7 +499,7 @@ __global__ __launch_bounds__(256, LK_DBWD_MINB) void k_decode_bwd(LkDecodeBwdArg
             if (a.affine && a.g_affine && threadIdx.x < 12) a.g_affine_part[(size_t)bid * 12 + threadIdx.x] = 0.0f;
             return;
         }
-        decode_bwd_col_wg<H16, DEEP, !GH16>(a, bid, w, lk_lane(), s_x, s_o);
+        decode_bwd_col_wg<H16, DEEP, !GH16, SA>(a, bid, w, lk_lane(), s_x, s_o);
         return;
     }
     float (*s_part)[3 * EGP] = reinterpret_cast<float (*)[3 * EGP]>(s_x);
@@ -507,7 +510,7 @@ __global__ __launch_bounds__(256, LK_DBWD_MINB) void k_decode_bwd(LkDecodeBwdArg
         __syncthreads();
     }
     const int tile = gb * 4 + w;
-    if (tile * 32 < P_live) decode_bwd_geo_wave<GH16>(a, tile, s_part[w], s_x + 512 + w * (6 * 64));       // (s_part ends at s_x[288])
+    if (tile * 32 < P_live) decode_bwd_geo_wave<GH16, SA>(a, tile, s_part[w], s_x + 512 + w * (6 * 64));       // (s_part ends at s_x[288])
     if (want_w) {
         __syncthreads();
         for (int e = threadIdx.x; e < 3 * EGP; e += 256)

@@ -412,7 +412,7 @@ __device__ __forceinline__ void relpos_bwd_wave(const LkRelposBwdArgs& a, int sa
     LK_STAMPW(1);                                    // (probe build) lists, positions, feature rows arrived; embedding evaluated
     // the recomputed forward uses the forward kernels' fp16x3 products (operands of O(1): embedding, features, activations)
     const u32x4* __restrict__ FH = FB + FRAGB_U4;
-    RP_HIDDEN(hid, W, FH, x0, x1, lane)
+    RP_HIDDEN(hid, W, FH, x0, x1, lane, (LK_SPLIT_FMA != 0), false)
     LK_STAMP(2);                                     // hidden layer recomputed
     // ---- d out = w * dc ; (tracker) d w = dc . out
     f32x16 dout[1];

@@ -201,6 +201,49 @@ __device__ __forceinline__ float lk_cosf(float x) {
 // Inside a persistent-workgroup loop it makes what is derived from it loop-VARIANT: the 64-bit addresses of a few dozen weight
 // fragment blocks are then formed where they are used instead of being hoisted out of the loop and spilled.
 __device__ __forceinline__ int lk_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
+// -1.0f the optimiser cannot see through, in a SCALAR register (lk_f16_rem).  The statement is not volatile and has no input but the
+// constant: every copy of it in a kernel is the same expression to the compiler, which keeps one (one s_mov per kernel, hoisted out of
+// the loops), wherever the helper is called from.
+__device__ __forceinline__ float lk_opaque_m1() {
+#if defined(__AMDGCN__)
+    float m;
+    asm("" : "=s"(m) : "0"(-1.0f));
+    return m;
+#else
+    return -1.0f;          // host pass and the CPU test build: no scalar registers, and nothing to gain
+#endif
+}
+
+// ------------------------------------------------------------------ uniform base + lane offset ("saddr") loads
+// A weight fragment block, a bias or an output-weight vector sits at (address every lane of the wave shares) + (lane part that never changes).
+// Written as one pointer expression the compiler keeps a 64-bit per-lane address in vector registers and re-adds the block offset to it with
+// vector instructions (the fully unrolled decoders: one v_add_co / v_addc_co pair every second fragment, the immediate offset reaches 4 KB and
+// the blocks lie 2 KB apart).  lk_sbase hands it the uniform part in a SCALAR register pair it cannot merge back (an empty statement; not
+// volatile: equal bases are one value) and in the global address space, and the access becomes global_load v, v_lane, s[base:base+1] offset:imm
+// - the stepping from block to block is s_add_u32 / s_addc_u32.  A base that is uniform by construction but lives in a vector register (derived
+// from the wave index) is brought there by reading the block index from the first lane.  It is a PER-KERNEL choice, the template parameter SADDR
+// of the loaders below (default: the plain pointer form, the same loads): the kernels that name it are the ones it made shorter alone on the chip -
+// the tracker's k_relpos_decode_fwd and k_decode_bwd - and the others it lengthened or cost a register step (profiles/valu_diet.md).
+// -DLK_FRAG_SADDR=0 switches it off in those too (the A side of a timing comparison).
+#ifndef LK_FRAG_SADDR
+#define LK_FRAG_SADDR 1
+#endif
+#if defined(__AMDGCN__)
+typedef const __attribute__((address_space(1))) char* lk_gbytes;
+typedef float lk_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ lk_gbytes lk_sbase(const void* p, size_t byte_off) {
+    uint64_t b = reinterpret_cast<uint64_t>(p) + byte_off;
+    asm("" : "=s"(b) : "0"(b));
+    return (lk_gbytes)b;
+}
+template <class T>
+__device__ __forceinline__ T lk_sload(lk_gbytes base, unsigned lane_off) {
+    return *reinterpret_cast<const __attribute__((address_space(1))) T*>(base + lane_off);
+}
+#define LK_SADDR_DEVICE 1
+#else
+#define LK_SADDR_DEVICE 0          // host pass and the CPU test build: plain pointers
+#endif
 
 // Four consecutive channels of a feature row, element index e (a multiple of 4) into the table: fp32 tables, or - opt-in,
 // LK_FLAG_FEATS_F16 - IEEE half tables (8 bytes, exact conversion).  `f16` is uniform over the launch.
@@ -287,49 +330,79 @@ __device__ __forceinline__ f32x16 lk_mma6(const LkB8& a, const LkB8& b, f32x16 a
 }
 // split-fragment block (G, nb) of a matrix: fragb = first block of the matrix form (lkw::FMxx_FWDB / _TRB, uint4 units
 // behind the fp32 fragments), NBT = blocks per G
+template <bool SADDR = false>
 __device__ __forceinline__ LkB8 lk_fragb_load(const u32x4* __restrict__ fragb, int NBT, int G, int nb, int lane) {
-    const u32x4* __restrict__ q = fragb + ((size_t)G * NBT + nb) * 192 + lane;
     LkB8 a;
+#if LK_SADDR_DEVICE
+    if (SADDR) {
+        const lk_gbytes q = lk_sbase(fragb, (size_t)lk_uniform(G * NBT + nb) * (192 * 16));
+        const unsigned lo = (unsigned)lane * 16u;
+        a.p[0] = lk_sload<u32x4>(q, lo); a.p[1] = lk_sload<u32x4>(q, lo + 1024u); a.p[2] = lk_sload<u32x4>(q, lo + 2048u);
+        return a;
+    }
+#endif
+    const u32x4* __restrict__ q = fragb + ((size_t)G * NBT + nb) * 192 + lane;
     a.p[0] = q[0]; a.p[1] = q[64]; a.p[2] = q[128];
     return a;
 }
 // acc[nb] += W[nb0 + nb][G0 .. G0+NGG) X  for the NGG 16-k blocks taken from registers of x starting at block XG0
-template <int NB, int NGG>
+template <int NB, int NGG, bool SADDR = false>
 __device__ __forceinline__ void lk_gemm_b6(f32x16 (&acc)[NB], const u32x4* __restrict__ fragb, int NBT, int G0, int nb0,
                                            const f32x16& x, int XG0, int lane) {
 #pragma unroll
     for (int G = 0; G < NGG; ++G) {
         const LkB8 b = lk_split_ct(x, XG0 + G);
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = lk_mma6(lk_fragb_load(fragb, NBT, G0 + G, nb0 + nb, lane), b, acc[nb]);
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = lk_mma6(lk_fragb_load<SADDR>(fragb, NBT, G0 + G, nb0 + nb, lane), b, acc[nb]);
     }
 }
 
 // ------------------------------------------------------------------ forward products as fp16x3
-// Two fp16 pieces per value (hi = rtz_f16(x) by pack-convert, lo = rtz_f16(x - hi): 22 significand bits, 3 VALU
-// instructions per value instead of 5.5) and three products hi.hi + hi.lo + lo.hi: measured 1.7e-7 sum|ab| against fp64 on
+// Two fp16 pieces per value (hi = rtz_f16(x) by pack-convert, lo = rtz_f16(x - hi): 22 significand bits, 2 VALU
+// instructions per value instead of 5.5: lk_f16_rem) and three products hi.hi + hi.lo + lo.hi: measured 1.7e-7 sum|ab| against fp64 on
 // O(1) data - the same as bf16x6 - at half the matrix instructions.  fp16 has a narrow exponent: the low piece of
 // |x| < 0.1 is a subnormal (absolute error <= 3e-8 per element instead of relative 2^-22) and |x| > 65 504 saturates, which
 // is harmless for the forward operands (Fourier features, interpolated point features, activations, weights: O(1e-3 .. 10))
 // and is why the BACKWARD kernels, whose operands are gradients of arbitrary scale, stay on the bf16 pieces.
+// Remainder of the two-piece cut, x - (float)h with ONE rounding: fma((float)h, -1, x) - the product is exact, so this is the subtraction's
+// result bit for bit (signed zeros, denormals, inf - inf and NaN included: tests/test_split_forms.py).  Written as a subtraction, or with a
+// literal -1, it compiles to v_cvt_f32_f16 + v_sub_f32; with the factor opaque in a scalar register it is one v_fma_mix_f32, which reads
+// the half operand (either half of a pack-convert's register) directly: one VALU instruction per value instead of two.
+// hf = (float)h at the call site (the conversion folds into the instruction's operand select).
+__device__ __forceinline__ float lk_f16_rem(float x, float hf) { return __builtin_fmaf(hf, lk_opaque_m1(), x); }
+// one pair of values: hi = rtz_f16 of the pair, lo = rtz_f16 of the remainders, each as a packed register.
+// FMA = false is the convert-and-subtract form, the same bits: for a kernel that the fma form moves across a register step (the compiler
+// schedules the shorter chain differently) - k_relpos_fwd_checked is the only one, profiles/valu_diet.md.  -DLK_SPLIT_FMA=0 builds the whole
+// library that way (the A side of a timing comparison).
+#ifndef LK_SPLIT_FMA
+#define LK_SPLIT_FMA 1
+#endif
+template <bool FMA = (LK_SPLIT_FMA != 0)>
+__device__ __forceinline__ void lk_cut2h(float x, float y, unsigned& hi, unsigned& lo) {
+    const lk_f16x2 h = __builtin_amdgcn_cvt_pkrtz(x, y);
+    const float hx = (float)h[0], hy = (float)h[1];
+    const lk_f16x2 l = FMA ? __builtin_amdgcn_cvt_pkrtz(lk_f16_rem(x, hx), lk_f16_rem(y, hy)) : __builtin_amdgcn_cvt_pkrtz(x - hx, y - hy);
+    hi = __builtin_bit_cast(unsigned, h); lo = __builtin_bit_cast(unsigned, l);
+}
 struct LkH8 { u32x4 p[2]; };
+template <bool FMA = (LK_SPLIT_FMA != 0)>
 __device__ __forceinline__ LkH8 lk_split8h(const float (&v)[8]) {
     LkH8 s;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const lk_f16x2 h = __builtin_amdgcn_cvt_pkrtz(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - (float)h[0], r1 = v[2 * i + 1] - (float)h[1];
-        const lk_f16x2 l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
-        s.p[0][i] = __builtin_bit_cast(unsigned, h);
-        s.p[1][i] = __builtin_bit_cast(unsigned, l);
+        unsigned hi, lo;
+        lk_cut2h<FMA>(v[2 * i], v[2 * i + 1], hi, lo);
+        s.p[0][i] = hi;
+        s.p[1][i] = lo;
     }
     return s;
 }
+template <bool FMA = (LK_SPLIT_FMA != 0)>
 __device__ __forceinline__ LkH8 lk_split_cth(const f32x16& x, int G) {
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = x[8 * G + i];
-    return lk_split8h(v);
+    return lk_split8h<FMA>(v);
 }
 __device__ __forceinline__ f32x16 lk_mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(lk_f16x8, a), __builtin_bit_cast(lk_f16x8, b), c, 0, 0, 0);
@@ -341,20 +414,29 @@ __device__ __forceinline__ f32x16 lk_mma3h(const LkH8& a, const LkH8& b, f32x16 
     return acc;
 }
 // fp16 forward-fragment block (G, nb): fragh = first block of the matrix (lkw::FMxx_FWDH, uint4 units behind the bf16 blob)
+template <bool SADDR = false>
 __device__ __forceinline__ LkH8 lk_fragh_load(const u32x4* __restrict__ fragh, int NBT, int G, int nb, int lane) {
-    const u32x4* __restrict__ q = fragh + ((size_t)G * NBT + nb) * 128 + lane;
     LkH8 a;
+#if LK_SADDR_DEVICE
+    if (SADDR) {
+        const lk_gbytes q = lk_sbase(fragh, (size_t)lk_uniform(G * NBT + nb) * (128 * 16));
+        const unsigned lo = (unsigned)lane * 16u;
+        a.p[0] = lk_sload<u32x4>(q, lo); a.p[1] = lk_sload<u32x4>(q, lo + 1024u);
+        return a;
+    }
+#endif
+    const u32x4* __restrict__ q = fragh + ((size_t)G * NBT + nb) * 128 + lane;
     a.p[0] = q[0]; a.p[1] = q[64];
     return a;
 }
-template <int NB, int NGG>
+template <int NB, int NGG, bool FMA = (LK_SPLIT_FMA != 0), bool SADDR = false>
 __device__ __forceinline__ void lk_gemm_h3(f32x16 (&acc)[NB], const u32x4* __restrict__ fragh, int NBT, int G0, int nb0,
                                            const f32x16& x, int XG0, int lane) {
 #pragma unroll
     for (int G = 0; G < NGG; ++G) {
-        const LkH8 b = lk_split_cth(x, XG0 + G);
+        const LkH8 b = lk_split_cth<FMA>(x, XG0 + G);
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = lk_mma3h(lk_fragh_load(fragh, NBT, G0 + G, nb0 + nb, lane), b, acc[nb]);
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = lk_mma3h(lk_fragh_load<SADDR>(fragh, NBT, G0 + G, nb0 + nb, lane), b, acc[nb]);
     }
 }
 
@@ -427,22 +509,35 @@ __device__ __forceinline__ uint64_t lk_dpp_u64(uint64_t v) {
 
 // CT tile whose 16 registers are a per-row vector (bias): the start value of an accumulator - the bias add then costs no
 // VALU instruction at all (four 16-byte loads land in the accumulator registers)
+// float4 at v[unit0 + 8 g + 4 h]: v + unit0 is the same in every lane (a bias, an output-weight vector), the lane part is the half-wave's 16 bytes
+template <bool SADDR = false>
+__device__ __forceinline__ float4 lk_rowvec4(const float* __restrict__ v, int unit0, int g, int h) {
+#if LK_SADDR_DEVICE
+    if (SADDR) {
+        const lk_f32x4 b = lk_sload<lk_f32x4>(lk_sbase(v, (size_t)lk_uniform(unit0) * 4), (unsigned)h * 16u + (unsigned)g * 32u);
+        return make_float4(b[0], b[1], b[2], b[3]);
+    }
+#endif
+    return *reinterpret_cast<const float4*>(v + unit0 + 8 * g + 4 * h);
+}
+template <bool SADDR = false>
 __device__ __forceinline__ f32x16 lk_rowvec_tile(const float* __restrict__ v, int unit0, int lane) {
     const int h = lane >> 5;
     f32x16 t;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const float4 b = *reinterpret_cast<const float4*>(v + unit0 + 8 * g + 4 * h);
+        const float4 b = lk_rowvec4<SADDR>(v, unit0, g, h);
         t[4 * g + 0] = b.x; t[4 * g + 1] = b.y; t[4 * g + 2] = b.z; t[4 * g + 3] = b.w;
     }
     return t;
 }
 // per-row vector (bias) of a CT tile: v[unit(r,h)] for r = 0..15, unit0 = first unit of the tile
+template <bool SADDR = false>
 __device__ __forceinline__ void lk_add_rowvec(f32x16& acc, const float* __restrict__ v, int unit0, int lane) {
     const int h = lane >> 5;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const float4 b = *reinterpret_cast<const float4*>(v + unit0 + 8 * g + 4 * h);
+        const float4 b = lk_rowvec4<SADDR>(v, unit0, g, h);
         acc[4 * g + 0] += b.x; acc[4 * g + 1] += b.y; acc[4 * g + 2] += b.z; acc[4 * g + 3] += b.w;
     }
 }

@@ -87,7 +87,8 @@ __device__ __forceinline__ f32x16 sincos_embed_tile(const float* __restrict__ B,
 }
 
 // bias + activation (+ optional save) + fc_c(c): h = act(acc + b) + (U c + u); c arrives as its two split blocks
-template <int NB, bool SOFTPLUS>
+// SA: the addressing form of the loads (lk_common.h: lk_sbase), chosen by the kernel
+template <int NB, bool SOFTPLUS, bool SA = false>
 __device__ __forceinline__ void layer_finish(f32x16 (&acc)[NB],
                                              const u32x4* __restrict__ UfragB, const float* __restrict__ ubias,
                                              const LkH8 (&cb)[2], float* __restrict__ save_a, bool live, int lane) {
@@ -96,9 +97,9 @@ __device__ __forceinline__ void layer_finish(f32x16 (&acc)[NB],
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][r] = SOFTPLUS ? lk_softplus100(acc[nb][r]) : fmaxf(acc[nb][r], 0.0f);
         if (save_a) ct_store_rows32(save_a + nb * 32, acc[nb], live, lane);
-        lk_add_rowvec(acc[nb], ubias, nb * 32, lane);
+        lk_add_rowvec<SA>(acc[nb], ubias, nb * 32, lane);
 #pragma unroll
-        for (int G = 0; G < 2; ++G) acc[nb] = lk_mma3h(lk_fragh_load(UfragB, NB, G, nb, lane), cb[G], acc[nb]);
+        for (int G = 0; G < 2; ++G) acc[nb] = lk_mma3h(lk_fragh_load<SA>(UfragB, NB, G, nb, lane), cb[G], acc[nb]);
     }
 }
 
@@ -126,7 +127,7 @@ __device__ __forceinline__ DecSample dec_sample(const LkDecodeArgs& a, int tile,
 }
 
 // ================= geometry decoder (hidden 32, relu): one wave = one 32-sample tile, registers only =================
-template <bool CHECK = false>
+template <bool CHECK = false, bool SA = false>
 __device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile, int lane) {      // returns the occupancy of lane & 31's sample
     const DecSample d = dec_sample(a, tile, lane);
     const int h = d.h, sp = d.sp;
@@ -152,38 +153,38 @@ __device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile
     LK_STAMPW(5);                                    // (probe build) geometry wave: embedding evaluated, c_geo arrived
     f32x16 acc[1], hh;
     // layer 0: 93 -> 32
-    acc[0] = lk_rowvec_tile(W + G_B0, 0, lane);
+    acc[0] = lk_rowvec_tile<SA>(W + G_B0, 0, lane);
 #pragma unroll
-    for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load(FB + FM0_FWDH, 1, G, 0, lane), eb[G], acc[0]);
-    layer_finish<1, false>(acc, FB + FM5_FWDH, W + G_U0 + a64(HG * CF), cb, act_geo, live, lane);
+    for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load<SA>(FB + FM0_FWDH, 1, G, 0, lane), eb[G], acc[0]);
+    layer_finish<1, false, SA>(acc, FB + FM5_FWDH, W + G_U0 + a64(HG * CF), cb, act_geo, live, lane);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(6);
     // layers 1, 2: 32 -> 32
-    acc[0] = lk_rowvec_tile(W + G_B1, 0, lane);
-    lk_gemm_h3<1, 2>(acc, FB + FM1_FWDH, 1, 0, 0, hh, 0, lane);
-    layer_finish<1, false>(acc, FB + FM6_FWDH, W + G_U0 + G_USTRIDE + a64(HG * CF), cb,
+    acc[0] = lk_rowvec_tile<SA>(W + G_B1, 0, lane);
+    lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM1_FWDH, 1, 0, 0, hh, 0, lane);
+    layer_finish<1, false, SA>(acc, FB + FM6_FWDH, W + G_U0 + G_USTRIDE + a64(HG * CF), cb,
                            act_geo ? act_geo + 32 : nullptr, live, lane);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(7);
-    acc[0] = lk_rowvec_tile(W + G_B2, 0, lane);
-    lk_gemm_h3<1, 2>(acc, FB + FM2_FWDH, 1, 0, 0, hh, 0, lane);
-    layer_finish<1, false>(acc, FB + FM7_FWDH, W + G_U0 + 2 * G_USTRIDE + a64(HG * CF), cb,
+    acc[0] = lk_rowvec_tile<SA>(W + G_B2, 0, lane);
+    lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM2_FWDH, 1, 0, 0, hh, 0, lane);
+    layer_finish<1, false, SA>(acc, FB + FM7_FWDH, W + G_U0 + 2 * G_USTRIDE + a64(HG * CF), cb,
                            act_geo ? act_geo + 64 : nullptr, live, lane);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(8);
     // layer 3 (skip): [e(93) | h(32)] -> 32, packed as [96 | 32]
-    acc[0] = lk_rowvec_tile(W + G_B3, 0, lane);
+    acc[0] = lk_rowvec_tile<SA>(W + G_B3, 0, lane);
 #pragma unroll
-    for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load(FB + FM3_FWDH, 1, G, 0, lane), eb[G], acc[0]);
-    lk_gemm_h3<1, 2>(acc, FB + FM3_FWDH, 1, 6, 0, hh, 0, lane);
-    layer_finish<1, false>(acc, FB + FM8_FWDH, W + G_U0 + 3 * G_USTRIDE + a64(HG * CF), cb,
+    for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load<SA>(FB + FM3_FWDH, 1, G, 0, lane), eb[G], acc[0]);
+    lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM3_FWDH, 1, 6, 0, hh, 0, lane);
+    layer_finish<1, false, SA>(acc, FB + FM8_FWDH, W + G_U0 + 3 * G_USTRIDE + a64(HG * CF), cb,
                            act_geo ? act_geo + 96 : nullptr, live, lane);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(9);
     // layer 4
-    acc[0] = lk_rowvec_tile(W + G_B4, 0, lane);
-    lk_gemm_h3<1, 2>(acc, FB + FM4_FWDH, 1, 0, 0, hh, 0, lane);
-    layer_finish<1, false>(acc, FB + FM9_FWDH, W + G_U0 + 4 * G_USTRIDE + a64(HG * CF), cb,
+    acc[0] = lk_rowvec_tile<SA>(W + G_B4, 0, lane);
+    lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM4_FWDH, 1, 0, 0, hh, 0, lane);
+    layer_finish<1, false, SA>(acc, FB + FM9_FWDH, W + G_U0 + 4 * G_USTRIDE + a64(HG * CF), cb,
                            act_geo ? act_geo + 128 : nullptr, live, lane);
     // output 32 -> 1 on the VALU: each half-wave holds 16 of the 32 units of its sample
     float part = 0.0f;
@@ -373,27 +374,21 @@ __device__ __forceinline__ void decode_col_setup(const LkDecodeArgs& a, int tile
         *reinterpret_cast<float4*>(erow + 8 * w + 4 * h) = make_float4(ev[0], ev[1], ev[2], ev[3]);
         if (w == 3) *reinterpret_cast<float4*>(erow + 32 + 4 * h) = make_float4(e1v[0], e1v[1], e1v[2], e1v[3]);
     }
-    // the same cut as lk_split8h: hi = rtz_f16 of the pair, lo = rtz_f16 of the remainders
-    auto cut2 = [&](float x, float y, unsigned& hi, unsigned& lo) {
-        const lk_f16x2 hh = __builtin_amdgcn_cvt_pkrtz(x, y);
-        const lk_f16x2 ll = __builtin_amdgcn_cvt_pkrtz(x - (float)hh[0], y - (float)hh[1]);
-        hi = __builtin_bit_cast(unsigned, hh); lo = __builtin_bit_cast(unsigned, ll);
-    };
     unsigned* se = reinterpret_cast<unsigned*>(s_x[1]);
     unsigned hi0, lo0, hi1, lo1;
-    cut2(ev[0], ev[1], hi0, lo0); cut2(ev[2], ev[3], hi1, lo1);
+    lk_cut2h(ev[0], ev[1], hi0, lo0); lk_cut2h(ev[2], ev[3], hi1, lo1);          // the cut of lk_split8h
     const int G = w >> 1, c0 = 2 * (w & 1);
     *reinterpret_cast<uint2*>(se + ((G * 2 + 0) * 64 + lane) * 4 + c0) = make_uint2(hi0, hi1);
     *reinterpret_cast<uint2*>(se + ((G * 2 + 1) * 64 + lane) * 4 + c0) = make_uint2(lo0, lo1);
     if (w == 3) {
-        cut2(e1v[0], e1v[1], hi0, lo0); cut2(e1v[2], e1v[3], hi1, lo1);
+        lk_cut2h(e1v[0], e1v[1], hi0, lo0); lk_cut2h(e1v[2], e1v[3], hi1, lo1);
         s_x[1][(2 * 2 + 0) * 64 + lane] = u32x4{hi0, hi1, 0u, 0u};
         s_x[1][(2 * 2 + 1) * 64 + lane] = u32x4{lo0, lo1, 0u, 0u};
     }
 }
 
 // PRESET: the caller has run decode_col_setup for this tile already (k_relpos_decode_fwd)
-template <bool DEEP, bool SOFTBAR = false, bool CHECK = false, bool PRESET = false>
+template <bool DEEP, bool SOFTBAR = false, bool CHECK = false, bool PRESET = false, bool SA = false>
 __device__ __forceinline__ void decode_col_wg(const LkDecodeArgs& a, int tile, int w, int lane,
                                               u32x4 (*s_x)[16 * 64] /* [2][16*64] */, float (*s_o)[3 * 32] /* [4][96] */,
                                               float (*s_bias)[128] /* [10][128] */, unsigned* s_cnt = nullptr, float* s_raw = nullptr) {
@@ -442,15 +437,15 @@ __device__ __forceinline__ void decode_col_wg(const LkDecodeArgs& a, int tile, i
     LkH8 wn[NPF], un[2], we[DEEP ? 3 : 1];
     auto prefetch_hidden = [&](const u32x4* fragb, int G0) {
 #pragma unroll
-        for (int G = 0; G < NPF; ++G) wn[G] = lk_fragh_load(fragb, 4, G0 + G, w, lane);
+        for (int G = 0; G < NPF; ++G) wn[G] = lk_fragh_load<SA>(fragb, 4, G0 + G, w, lane);
         if (DEEP && G0 == 3) {
 #pragma unroll
-            for (int G = 0; G < 3; ++G) we[G] = lk_fragh_load(fragb, 4, G, w, lane);
+            for (int G = 0; G < 3; ++G) we[G] = lk_fragh_load<SA>(fragb, 4, G, w, lane);
         }
     };
     auto prefetch_u = [&](const u32x4* ufragb) {
 #pragma unroll
-        for (int G = 0; G < 2; ++G) un[G] = lk_fragh_load(ufragb, 4, G, w, lane);
+        for (int G = 0; G < 2; ++G) un[G] = lk_fragh_load<SA>(ufragb, 4, G, w, lane);
     };
     // acc += W[own block][hidden 128] h with h read from LDS; G0 = first 16-k block of the hidden part in the matrix
     auto hidden = [&](f32x16& acc, const u32x4* fragb, int G0, int buf) {
@@ -459,12 +454,12 @@ __device__ __forceinline__ void decode_col_wg(const LkDecodeArgs& a, int tile, i
             LkH8 b;
 #pragma unroll
             for (int q = 0; q < 2; ++q) b.p[q] = s_x[buf][(G * 2 + q) * 64 + lane];
-            acc = lk_mma3h(G < NPF ? wn[G] : lk_fragh_load(fragb, 4, G0 + G, w, lane), b, acc);
+            acc = lk_mma3h(G < NPF ? wn[G] : lk_fragh_load<SA>(fragb, 4, G0 + G, w, lane), b, acc);
         }
     };
     auto embed = [&](f32x16& acc, const u32x4* fragb, bool fetched) {
 #pragma unroll
-        for (int G = 0; G < 3; ++G) acc = lk_mma3h((DEEP && fetched) ? we[G] : lk_fragh_load(fragb, 4, G, w, lane), eb[G], acc);
+        for (int G = 0; G < 3; ++G) acc = lk_mma3h((DEEP && fetched) ? we[G] : lk_fragh_load<SA>(fragb, 4, G, w, lane), eb[G], acc);
     };
     // bias + softplus + fc_c(c) for the wave's own 32-unit block, then ALL stores of the layer: saved a / h rows, LDS park
     auto finish = [&](f32x16& acc, unsigned* save_s, int L, int buf) {
@@ -609,7 +604,9 @@ __global__ __launch_bounds__(256, 2) void k_decode_fwd(LkDecodeArgs a, int n_col
 // ---------------------------------------------------------------------------------------------
 // Relative-position neighbour MLP: one wave = 32 neighbour rows = 4 samples x 8 neighbours.
 //   x_j = [sin(2 pi D_j B_r), cos(2 pi D_j B_r), F[I_j]] (52) -> 128 softplus100 -> 32;  c = sum_j w_j f_j
-template <bool CHECK = false>
+// FMA: the form of the fp16 cut's remainder in the hidden layer (lk_common.h: lk_cut2h; the same bits).  k_relpos_fwd_checked keeps the
+// convert-and-subtract form there: with the fma form the compiler takes 172 registers for it instead of 152 - two workgroups per unit, not three
+template <bool CHECK = false, bool FMA = (LK_SPLIT_FMA != 0), bool SA = false>
 __device__ __forceinline__ void relpos_fwd_wave(const LkRelposArgs& a, int sample0, int P) {
     const int lane = lk_lane();
     RP_ROW_SETUP(a, sample0, P, lane, false)         // the weight of every filled slot: `has` is applied where c is stored
@@ -618,14 +615,14 @@ __device__ __forceinline__ void relpos_fwd_wave(const LkRelposArgs& a, int sampl
     RP_INPUT_TILES(x0, x1, W, a.col_feats, a.feats_f16 != 0, true)
     ct_check_range<CHECK>(x0, a.status); ct_check_range<CHECK>(x1, a.status);
     LK_STAMPW(1);                                    // (probe build) lists, positions and feature rows arrived, embedding evaluated
-    RP_HIDDEN(hid, W, FB, x0, x1, lane)
+    RP_HIDDEN(hid, W, FB, x0, x1, lane, FMA, SA)
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) ct_check_range<CHECK>(hid[nb], a.status);
     LK_STAMP(2);
     f32x16 out[1];
-    out[0] = lk_rowvec_tile(W + R_B2, 0, lane);
+    out[0] = lk_rowvec_tile<SA>(W + R_B2, 0, lane);
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) lk_gemm_h3<1, 2>(out, FB + FM21_FWDH, 1, 2 * kb, 0, hid[kb], 0, lane);
+    for (int kb = 0; kb < 4; ++kb) lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(out, FB + FM21_FWDH, 1, 2 * kb, 0, hid[kb], 0, lane);
     // c[ch] = sum over the 8 neighbour rows of a sample (8 consecutive lanes) of w * f[ch]
     const bool kept = rp_has(a, sp);
     float* __restrict__ crow = a.c_col + (size_t)sp * LK_C;
@@ -652,7 +649,7 @@ __device__ __forceinline__ void relpos_fwd_kernel(const LkRelposArgs& a) {
     const int sample0 = wave * 4;
     const int P = a.live_rays ? min(a.P, *a.live_rays * a.S) : a.P;      // rays without a reading sit behind the live prefix: skipped
     if (sample0 >= P) return;
-    relpos_fwd_wave<CHECK>(a, sample0, P);
+    relpos_fwd_wave<CHECK, (LK_SPLIT_FMA != 0) && !CHECK>(a, sample0, P);
 }
 __global__ __launch_bounds__(256) void k_relpos_fwd(LkRelposArgs a) { relpos_fwd_kernel<false>(a); }
 __global__ __launch_bounds__(256) void k_relpos_fwd_checked(LkRelposArgs a) { relpos_fwd_kernel<true>(a); }       // LK_FLAG_CHECK_RANGE
@@ -684,6 +681,9 @@ __global__ __launch_bounds__(512) void k_relpos_decode_fwd(LkRelposArgs ra, LkDe
     __shared__ __attribute__((aligned(16))) float s_raw[32 * 4];
     __shared__ u32x4 s_gw[GLDS ? LK_GEO_STAGE_BLOCKS * 128 : 1];
     __shared__ __attribute__((aligned(16))) float s_gb[GLDS ? 10 : 1][32];
+    // scalar-base fragment loads (lk_common.h: lk_sbase) in all three bodies of this launch: one tile's dependent chain at one wave per SIMD, where
+    // the vector instructions they save are on the critical path (31.9 -> 31.5 us alone; k_decode_fwd and k_relpos_fwd got longer with them)
+    constexpr bool SA = (LK_FRAG_SADDR != 0);
     const int lane = lk_lane();
     const int w = (int)threadIdx.x >> 6;
     const int tile = (int)blockIdx.x;
@@ -695,13 +695,13 @@ __global__ __launch_bounds__(512) void k_relpos_decode_fwd(LkRelposArgs ra, LkDe
     LK_STAMP(0);
     if (w < 4) decode_col_setup(a, tile, w, lane, s_x, s_bias);      // (in front of the rel-pos MLP: its fetches are cold, and independent of it)
     if (GLDS) lk_geo_stage(a, w, lane, s_gw, s_gb);                  // the geometry decoder's operands into LDS (decode_geo_wave_lds)
-    if (sample0 < lim) relpos_fwd_wave(ra, sample0, lim);
+    if (sample0 < lim) relpos_fwd_wave<false, (LK_SPLIT_FMA != 0), SA>(ra, sample0, lim);
     LK_STAMP(3);
     __syncthreads();                               // the tile's c_col rows are written
     LK_STAMP(4);
     if (w > 4) return;
     if (w == 4) {
-        const float occ = GLDS ? decode_geo_wave_lds(a, tile, lane, s_gw, s_gb) : decode_geo_wave(a, tile, lane);
+        const float occ = GLDS ? decode_geo_wave_lds(a, tile, lane, s_gw, s_gb) : decode_geo_wave<false, SA>(a, tile, lane);
         if (COMP) {
             if (lane < 32) s_raw[4 * lane + 3] = occ;
             __builtin_amdgcn_wave_barrier();       // (the host emulation runs lanes as fibers: every lane's row before lane 0's signal)
@@ -725,7 +725,7 @@ __global__ __launch_bounds__(512) void k_relpos_decode_fwd(LkRelposArgs ra, LkDe
             if (s < S) { cz[s] = tl.z[base + lane * S + s]; chas[s] = tl.nbr_count[base + lane * S + s] >= tl.min_nn; }
         }
     }
-    decode_col_wg<DEEP, true, false, true>(a, tile, w, lane, s_x, s_o, s_bias, &s_cnt, COMP ? s_raw : nullptr);
+    decode_col_wg<DEEP, true, false, true, SA>(a, tile, w, lane, s_x, s_o, s_bias, &s_cnt, COMP ? s_raw : nullptr);
     if (COMP && w == 0) {
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();

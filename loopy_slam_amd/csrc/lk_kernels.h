@@ -4,21 +4,22 @@
 
 // the piece type of a backward product chain: three bf16 pieces (lk_mma6: any scale) or two fp16 pieces of a PRE-SCALED chain (lk_mma3h: unit-scale
 // loss gradients times 2^10) - decode_bwd_col_wg, decode_bwd_geo_wave (lk_bwd.hip), relpos_bwd_wave (lk_bwd2.hip)
-template <bool H16> struct BwdPiece;
-template <> struct BwdPiece<false> {
+// SADDR: the addressing form of the fragment loads (lk_common.h: lk_sbase), a per-kernel choice
+template <bool H16, bool SADDR = false> struct BwdPiece;
+template <bool SADDR> struct BwdPiece<false, SADDR> {
     typedef LkB8 T;
     static constexpr int NP = 3;
     static __device__ __forceinline__ T split(const f32x16& x, int G) { return lk_split_ct(x, G); }
     static __device__ __forceinline__ f32x16 mma(const T& a, const T& b, f32x16 c) { return lk_mma6(a, b, c); }
-    static __device__ __forceinline__ T load(const u32x4* f, int NBT, int G, int nb, int lane) { return lk_fragb_load(f, NBT, G, nb, lane); }
+    static __device__ __forceinline__ T load(const u32x4* f, int NBT, int G, int nb, int lane) { return lk_fragb_load<SADDR>(f, NBT, G, nb, lane); }
     static __device__ __forceinline__ int tr(int idx) { return lkw::FRAG_TRB[idx]; }
 };
-template <> struct BwdPiece<true> {
+template <bool SADDR> struct BwdPiece<true, SADDR> {
     typedef LkH8 T;
     static constexpr int NP = 2;
     static __device__ __forceinline__ T split(const f32x16& x, int G) { return lk_split_cth(x, G); }
     static __device__ __forceinline__ f32x16 mma(const T& a, const T& b, f32x16 c) { return lk_mma3h(a, b, c); }
-    static __device__ __forceinline__ T load(const u32x4* f, int NBT, int G, int nb, int lane) { return lk_fragh_load(f, NBT, G, nb, lane); }
+    static __device__ __forceinline__ T load(const u32x4* f, int NBT, int G, int nb, int lane) { return lk_fragh_load<SADDR>(f, NBT, G, nb, lane); }
     static __device__ __forceinline__ int tr(int idx) { return lkw::FRAG_TRH[idx]; }
 };
 

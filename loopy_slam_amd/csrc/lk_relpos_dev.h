@@ -76,11 +76,12 @@ __device__ __forceinline__ bool rp_has(const Args& a, int sp) { return a.nbr_cou
 
 // 3. Hidden layer hid[4] (declared here), unpipelined form (forward and plain backward): bias tiles, linear1 on fp16x3 pieces, softplus.
 //    FH: the fp16 forward fragments.  (The fused body keeps its fragment-ahead loop: another schedule, not a copy.)
-#define RP_HIDDEN(hid, W, FH, x0, x1, lane)                                                                         \
+//    FMA: the form of the fp16 cut's remainder (lk_common.h: lk_cut2h), SA: the addressing form of the loads (lk_sbase) - the same bits either way
+#define RP_HIDDEN(hid, W, FH, x0, x1, lane, FMA, SA)                                                                      \
     f32x16 hid[4];                                                                                                  \
-    _Pragma("unroll") for (int nb = 0; nb < 4; ++nb) hid[nb] = lk_rowvec_tile(W + R_B1, nb * 32, lane);   /* accumulators start from the bias */ \
-    lk_gemm_h3<4, 2>(hid, FH + FM20_FWDH, 4, 0, 0, x0, 0, lane);                                                    \
-    lk_gemm_h3<4, 2>(hid, FH + FM20_FWDH, 4, 2, 0, x1, 0, lane);      /* units 32..55; registers 12..15 of x1 are zero */ \
+    _Pragma("unroll") for (int nb = 0; nb < 4; ++nb) hid[nb] = lk_rowvec_tile<SA>(W + R_B1, nb * 32, lane);   /* accumulators start from the bias */ \
+    lk_gemm_h3<4, 2, FMA, SA>(hid, FH + FM20_FWDH, 4, 0, 0, x0, 0, lane);                                              \
+    lk_gemm_h3<4, 2, FMA, SA>(hid, FH + FM20_FWDH, 4, 2, 0, x1, 0, lane);     /* units 32..55; registers 12..15 of x1 are zero */ \
     _Pragma("unroll") for (int nb = 0; nb < 4; ++nb) {                                                              \
         _Pragma("unroll") for (int q = 0; q < 16; ++q) hid[nb][q] = lk_softplus100(hid[nb][q]);                     \
     }

@@ -5,6 +5,7 @@ almost fully unrolled, so the ratio of VALU to matrix instructions is what the S
     python tools/isa_mix.py k_decode_bwd            # classes
     python tools/isa_mix.py k_decode_bwd --top 40   # individual mnemonics
     python tools/isa_mix.py k_decode_bwd --dump /tmp/x.s
+    python tools/isa_mix.py k_decode --lib ab/lib_a.so --compare ab/lib_b.so    # one table row per kernel, a -> b (profiles/valu_diet.md)
 """
 import argparse
 import collections
@@ -72,16 +73,39 @@ def kernels(lib):
                 yield name, body
 
 
+def row(body):
+    """What profiles/valu_diet.md tabulates: vector instructions (matrix ones apart), the half -> float converts, v_fma_mix_f32, the 64-bit
+    address arithmetic (v_lshl_add_u64, v_add_co / v_addc_co), matrix instructions."""
+    c = collections.Counter(ln.split()[0] for ln in body if ln and not ln.startswith('//'))
+    tot = lambda *pre: sum(v for k, v in c.items() if k.startswith(pre))
+    return {'vector': tot('v_') - tot('v_mfma'), 'cvt_f32_f16': tot('v_cvt_f32_f16'), 'fma_mix': tot('v_fma_mix_f32'),
+            'addr64': tot('v_lshl_add_u64', 'v_add_co', 'v_addc_co'), 'mfma': tot('v_mfma')}
+
+
+def compare(lib_a, lib_b, flt):
+    a = {n: row(b) for n, b in kernels(lib_a) if flt in n}
+    b = {n: row(b) for n, b in kernels(lib_b) if flt in n}
+    cols = ('vector', 'cvt_f32_f16', 'fma_mix', 'addr64', 'mfma')
+    print('| kernel | ' + ' | '.join(cols) + ' |\n|---' * 1 + '|---' * len(cols) + '|')
+    for n in sorted(b):
+        short = n.split('(')[0].replace('void ', '')
+        print(f'| `{short}` | ' + ' | '.join(f"{a[n][k] if n in a else '-'} → {b[n][k]}" for k in cols) + ' |')
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('filter')
     ap.add_argument('--top', type=int, default=0)
     ap.add_argument('--dump')
     ap.add_argument('--lib', default=None)
+    ap.add_argument('--compare', metavar='LIB_B', help='table of the classes of profiles/valu_diet.md, --lib (default: the built library) -> LIB_B')
     a = ap.parse_args()
     if a.lib is None:
         from loopy_slam_amd.csrc import build
         a.lib = build.build()
+    if a.compare:
+        compare(a.lib, a.compare, a.filter)
+        sys.exit(0)
     for name, body in kernels(a.lib):
         if a.filter not in name:
             continue
