@@ -299,6 +299,8 @@ extern "C" int lk_track_frame(const lk_track_desc* d, void* stream_) {
     LK_REQUIRE(d != nullptr, "lk_track_frame: NULL descriptor");
     { const int rcg = lk_status_gate("lk_track_frame"); if (rcg != LK_OK) return rcg; }
     LK_REQUIRE(d->iters >= 0 && d->render.R >= 0 && d->w > 0, "lk_track_frame: bad sizes");
+    // (before the first launch: the batch assembly below runs ahead of the render's own check of its descriptor)
+    LK_REQUIRE(d->render.S >= 1 && d->render.S <= LK_S_MAX, "lk_track_frame: bad S (1 .. LK_S_MAX samples per ray)");
     if (d->iters == 0 || d->render.R == 0) return LK_OK;
     LK_REQUIRE(d->depth_img && d->color_img && d->rnd && d->cam7 && d->g_cam7 && d->adam_mv && d->hist && d->log, "lk_track_frame: NULL buffer");
     LK_REQUIRE(d->render.d_depth && d->render.d_color && d->render.bwd_scratch && d->render.act,
@@ -527,6 +529,7 @@ static void map_join_and_pregather(const lk_map_desc* d, const MapWork& wk, int 
 // The lk_map_frame call that follows (same descriptor values, batches_ready = 1, it_begin = 0) skips its own assembly.
 extern "C" int lk_map_prepare(const lk_map_desc* d, void* stream_) {
     LK_REQUIRE(d != nullptr && d->iters >= 0 && d->render.R >= 0, "lk_map_prepare: bad descriptor");
+    LK_REQUIRE(d->render.S >= 1 && d->render.S <= LK_S_MAX, "lk_map_prepare: bad S (1 .. LK_S_MAX samples per ray)");
     if (d->iters == 0 || d->render.R == 0) return LK_OK;
     LK_REQUIRE(d->work != nullptr && d->render.R <= LK_LOOP_MAX_R, "lk_map_prepare: needs `work` and at most 16384 rays");
     LK_REQUIRE(d->depth_stack && d->color_stack && d->c2w_stack && d->rnd && d->log, "lk_map_prepare: NULL batch buffer");
@@ -542,6 +545,8 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
     { const int rcg = lk_status_gate("lk_map_frame"); if (rcg != LK_OK) return rcg; }
     LK_REQUIRE(it_begin >= 0 && it_end <= d->iters && it_begin <= it_end && (phases & 3), "lk_map_frame: bad iteration range / phases");
     LK_REQUIRE(d->n_geo_dec >= 0 && d->n_geo_dec <= LK_MAX_SPANS && d->n_col_dec >= 0 && d->n_col_dec <= LK_MAX_SPANS, "lk_map_frame: too many spans");
+    // (before the first launch: the batch assembly and the look-ahead search run ahead of the render's own check of its descriptor)
+    LK_REQUIRE(d->render.R >= 0 && d->render.S >= 1 && d->render.S <= LK_S_MAX, "lk_map_frame: bad R/S (1 .. LK_S_MAX samples per ray)");
     if (it_begin == it_end || d->render.R == 0) return LK_OK;
     // a segment of a longer optimize_map call (lk_map_desc::it_offset): local iteration `it` is the call's iteration goff + it; the first
     // 'color' iteration has the local index n_geo_l (<= 0: the whole segment is 'color')

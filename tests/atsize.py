@@ -37,8 +37,8 @@ def ray_batch(R, frame=7, holes=0.0, seed=0, window=None):
     return dict(i=i, j=j, rays_o=ro, rays_d=rd, gt_depth=gd, gt_color=gc, c2w=c2w)
 
 
-def ocfg(rel_pos):
-    return H.RenderCfg(S=5, near_surface=0.98, far_surface=1.02, near_end=0.3, coef=0.1, k=8, min_nn=2,
+def ocfg(rel_pos, S=5):
+    return H.RenderCfg(S=S, near_surface=0.98, far_surface=1.02, near_end=0.3, coef=0.1, k=8, min_nn=2,
                        radius_query=0.08, rel_pos=rel_pos)
 
 

@@ -18,15 +18,15 @@ from util import load, tens, weights, CFG, CFG_NAMES, make_engine, backends
 torch.set_num_threads(1)
 
 
-def rcfg(name):
+def rcfg(name, S=5):
     c = CFG[name]
-    return core.RenderCfg(S=5, near_surface=c['near_surface'], far_surface=c['far_surface'], near_end=0.3,
+    return core.RenderCfg(S=S, near_surface=c['near_surface'], far_surface=c['far_surface'], near_end=0.3,
                           coef=0.1, min_nn=2, radius_query=0.08, rel_pos=c['rel_pos'], exposure=c['exposure'])
 
 
-def ocfg(name):
+def ocfg(name, S=5):
     c = CFG[name]
-    return H.RenderCfg(S=5, near_surface=c['near_surface'], far_surface=c['far_surface'], near_end=0.3, coef=0.1,
+    return H.RenderCfg(S=S, near_surface=c['near_surface'], far_surface=c['far_surface'], near_end=0.3, coef=0.1,
                        k=8, min_nn=2, radius_query=0.08, rel_pos=c['rel_pos'], exposure=c['exposure'])
 
 
@@ -176,10 +176,12 @@ def run_forward(eng, name, g, stage, tracker=False, affine=None, color_logits=Fa
     return st
 
 
-def check_outputs(st, g, has_color=True):
+def check_outputs(st, g, has_color=True, has_var=True):
+    """has_var False: the caller holds the variance another way (tests/test_sample_counts.py at one sample per ray)."""
     assert np.array_equal(st.valid_ray.cpu().numpy().astype(bool), g['valid_ray'])
     np.testing.assert_allclose(st.depth.cpu().numpy(), g['depth'], rtol=1e-4, atol=1e-6)
-    np.testing.assert_allclose(st.var.cpu().numpy(), g["var"], rtol=2e-4, atol=1e-9)       # the at-size bound (tests/test_parity_at_size.py: TOL_VAR)
+    if has_var:
+        np.testing.assert_allclose(st.var.cpu().numpy(), g["var"], rtol=2e-4, atol=1e-9)   # the at-size bound (tests/test_parity_at_size.py: TOL_VAR)
     if has_color:
         np.testing.assert_allclose(st.color.cpu().numpy(), g['color'], rtol=1e-4, atol=2e-5)
 

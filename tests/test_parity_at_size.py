@@ -46,12 +46,14 @@ REF_FLOOR_EL = 4e-3     # max |a - r64| / (|r64| + 1e-3 max |r64|)
 _REPORT = {}
 
 
-def _record(case, **kv):
-    _REPORT.setdefault(case, {}).update({k: (float(v) if not isinstance(v, (int, str)) else v) for k, v in kv.items()})
+def _record(case, _file='parity_at_size.json', _report=None, **kv):
+    """_file / _report: another module's report, written beside this one (tests/test_sample_counts.py)."""
+    _REPORT = globals()['_REPORT'] if _report is None else _report
+    _REPORT.setdefault(case, {}).update({k: (float(v) if not isinstance(v, (int, str, list, dict)) else v) for k, v in kv.items()})
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     if os.path.isdir(out):
-        with open(os.path.join(out, 'parity_at_size.json'), 'w') as f:
-            json.dump(_REPORT, f, indent=1, sort_keys=True)
+        with open(os.path.join(out, _file), 'w') as f:
+            json.dump(_REPORT, f, indent=1, sort_keys=True, default=float)
 
 
 def _gpu_scene(eng, N, rel_pos):
@@ -86,7 +88,9 @@ def _check_forward(st, o, case, gt_depth):
     np.testing.assert_allclose(st.var.cpu().numpy(), o['var'].detach().numpy(), rtol=TOL_VAR, atol=1e-9)
 
 
-def _check_grad(name, got, ref, case, skip_rows=None, tol=None, tol_el=None, ref64=None, floor_el=None):
+def _check_grad(name, got, ref, case, skip_rows=None, tol=None, tol_el=None, ref64=None, floor_el=None, record=None):
+    """record: another module's recorder in place of this module's _record (tests/test_sample_counts.py)."""
+    _record = globals()['_record'] if record is None else record
     got, ref = torch.as_tensor(got), torch.as_tensor(ref)
     if ref64 is not None:
         # the referee decides: both fp32 results against the float64 evaluation of the same graph on the same rounded inputs

@@ -31,23 +31,15 @@ def test_sizes_mirror_the_sources():
     fails here until the sizes of this module move with it (the render cases compare the forms of a launch with each other, so they are
     blind to a switch that has left the range of their batches).  The thresholds written as literals inside conditions are not read."""
     import os
-    import re
-    csrc = os.path.join(os.path.dirname(os.path.abspath(core.__file__)), 'csrc')
-
-    def src(name):
-        with open(os.path.join(csrc, name)) as f:
-            return f.read()
-
-    def define(text, name):
-        m = re.search(r'^#define\s+' + name + r'\s+\(?\s*(\d+)\s*(?:<<\s*(\d+))?\s*\)?\s*(?://.*)?$', text, re.M)         # 8192 or (1 << 14)
-        assert m, name
-        return int(m.group(1)) << int(m.group(2) or 0)
-    assert define(src('lk_mask_dev.h'), 'LK_MASK_REG_MAX') == sw.MASK_REG_MAX
-    assert define(src('lk_sample.hip'), 'LK_T16_MAX_P') == sw.T16_MAX_P
-    assert define(src('lk_kernels.h'), 'LK_DEEP_MAX_TILES') == define(src('lk_kernels.h'), 'LK_DEEP_MAX_TILES_FWD') == sw.DEEP_MAX_TILES
-    assert define(src('lk_kernels.h'), 'LK_COMPACT_ONE_BLOCK_MAX') == sw.COMPACT_ONE_BLOCK_MAX
-    header = src(os.path.join('..', '..', 'include', 'loopy_hip.h'))
+    define = sw.source_define                                                                                         # 8192 or (1 << 14)
+    assert define('lk_mask_dev.h', 'LK_MASK_REG_MAX') == sw.MASK_REG_MAX
+    assert define('lk_sample.hip', 'LK_T16_MAX_P') == sw.T16_MAX_P
+    assert define('lk_kernels.h', 'LK_DEEP_MAX_TILES') == define('lk_kernels.h', 'LK_DEEP_MAX_TILES_FWD') == sw.DEEP_MAX_TILES
+    assert define('lk_kernels.h', 'LK_COMPACT_ONE_BLOCK_MAX') == sw.COMPACT_ONE_BLOCK_MAX
+    header = os.path.join('..', '..', 'include', 'loopy_hip.h')
     assert define(header, 'LK_EXPOSURE_MAX_F') == sw.EXPOSURE_MAX_F and define(header, 'LK_ADAM_MAX_SEG') == sw.ADAM_MAX_SEG
+    # the counts of tests/test_sample_counts.py: every S the ABI accepts
+    assert define(header, 'LK_S_MAX') == sw.S_MAX == _ffi.LK_S_MAX
 
 
 # ---------------------------------------------------------------------------- A. lk_inside_mask
