@@ -187,7 +187,10 @@ typedef struct {
     float* c_col;               /* [P,32]  */
     float* raw;                 /* [P,4] rgb(or logits), occ */
     float* far_stats;           /* [ceil(R/stats_chunk)] */
-    float* act;                 /* SAVE_ACT: lk_render_act_floats(R,S,flags) floats, else NULL */
+    float* act;                 /* SAVE_ACT: lk_render_act_floats(R,S,flags) floats (16-byte aligned), else NULL.  lk_render_fwd leaves there what
+                                   lk_render_bwd reads: of the geometry trunk its relu bits (8 words per sample, read by every backward) and its
+                                   fp32 relu rows (read with LK_FLAG_GRAD_GEO_DECODER only; lk_track_frame and lk_map_frame without
+                                   train_geo_decoder do not write them), of the colour trunk the derivative mask, h_i rows and embedding */
     /* ---- backward inputs */
     const float* d_depth;       /* [R]   */
     const float* d_var;         /* [R] or NULL */
@@ -836,6 +839,12 @@ int lk_debug_side_delay(int32_t us);
  * pointers): hi / lo [n/2] = the packed pieces of the pairs (x[2i], x[2i+1]) in the production form, hi_ref / lo_ref [n/2] = the same
  * from the convert-and-subtract form it replaced (tests/test_split_forms.py: the two must agree bit for bit). */
 int lk_debug_split_forms(const float* x, int32_t n, uint32_t* hi, uint32_t* lo, uint32_t* hi_ref, uint32_t* lo_ref, void* stream);
+/* Test hook: the geometry trunk's saved relu bits (8 words per sample behind the act regions).  x [P][160] = five layers of 32 relu outputs per
+ * sample (device pointers throughout).  The production packer runs over x in the decoder forward's lane-to-sample mapping with tiles of
+ * `tile_stride` samples (32, or (32 / S) S as the tracker's fused forward) and leaves words [P][8]; the production reader then walks tiles of 32
+ * as the decoder backward does: dec [P][160] = 1 where it lets the gradient through, else 0; ref [P][160] = (x > 0.0f) from a plain kernel
+ * (tests/test_geo_act_bits.py: the two must be equal everywhere). */
+int lk_debug_geo_bits(const float* x, int32_t P, int32_t tile_stride, uint32_t* words, uint8_t* dec, uint8_t* ref, void* stream);
 
 #ifdef __cplusplus
 }

@@ -135,7 +135,7 @@ extern "C" int64_t lk_weight_blob_floats(void) { return BLOB_FLOATS; }
 
 extern "C" int64_t lk_render_act_floats(int32_t R, int32_t S, uint32_t flags) {
     (void)flags;
-    return (int64_t)R * S * LK_ACT_FLOATS_PER_SAMPLE;
+    return (int64_t)R * S * LK_ACT_WORDS_PER_SAMPLE;
 }
 
 // ------------------------------------------------------------------ backward scratch layout
@@ -247,6 +247,7 @@ int lk_render_fwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
     if (rc != LK_OK) return rc;
     if (d->R == 0) return LK_OK;
     LK_REQUIRE(d->depth && d->var && d->color && d->valid_ray, "lk_render_fwd: NULL output buffer");
+    LK_REQUIRE(((uintptr_t)d->act & 15u) == 0, "lk_render_fwd: act must be 16-byte aligned");      // (16-byte accesses in every region of it)
     const int P = d->R * d->S;
     const bool all_pos = (d->flags & (LK_FLAG_ALL_DEPTH_POS | LK_FLAG_ZERO_ABSENT)) != 0;
     if (!all_pos) {
@@ -281,6 +282,7 @@ int lk_render_fwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
     da.rays_o = d->rays_o; da.rays_d = d->rays_d; da.z = d->z;
     da.c_geo = d->c_geo; da.c_col = d->c_col; da.W = d->weights; da.Wfrag = d->weights_frag; da.affine = d->affine;
     da.raw = d->raw; da.act = d->act; da.live_rays = live_rays; da.tile_stride = 0;
+    da.geo_rows = (skip & LK_GEO_BITS_ONLY) ? 0 : 1;
     da.status = (d->flags & LK_FLAG_CHECK_RANGE) ? lk_status_dev() : nullptr;
     if (comp_tiles) *comp_tiles = 0;
     const bool fuse_small = (skip & LK_FUSE_SMALL) && lk_relpos_decode_fusable(da);
@@ -435,6 +437,56 @@ extern "C" int lk_debug_split_forms(const float* x, int32_t n, uint32_t* hi, uin
     LK_LAUNCH_CHECK();
     return LK_OK;
 }
+// Test hook (tests/test_geo_act_bits.py): the geometry trunk's relu bits (lk_kernels.h: LK_ACT_GEO_BITS).  k_geo_bits_pack holds a wave's tile as
+// the decoder forward does (sample = tile * tile_stride + (lane & 31), lanes >= tile_stride and samples >= P dead: clamped, never stored;
+// registers q = 4 g + t = units 8 g + 4 h + t) and runs the production packer and store; k_geo_bits_read walks tiles of 32 as the decoder
+// backward does, runs the production load and returns the decision it takes per value; k_gt_zero is the plain compare the bits stand for.
+__global__ __launch_bounds__(64) void k_geo_bits_pack(const float* __restrict__ x, int P, int ts, unsigned* __restrict__ region) {
+    const int lane = lk_lane(), h = lane >> 5;
+    const int sample = (int)blockIdx.x * ts + (lane & 31);
+    const bool live = sample < P && (lane & 31) < ts;
+    const int sp = live ? sample : P - 1;
+    LkGeoBits b = {{0u, 0u, 0u}};
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        f32x16 t;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 v = *reinterpret_cast<const float4*>(x + (size_t)sp * LK_ACT_GEO_A + 32 * i + 8 * g + 4 * h);
+            t[4 * g + 0] = v.x; t[4 * g + 1] = v.y; t[4 * g + 2] = v.z; t[4 * g + 3] = v.w;
+        }
+        lk_geo_bits_put(b, i, t);
+    }
+    lk_geo_bits_store(region, sample, h, b, live);
+}
+__global__ __launch_bounds__(64) void k_geo_bits_read(const unsigned* __restrict__ region, int P, uint8_t* __restrict__ dec) {
+    const int lane = lk_lane(), h = lane >> 5;
+    const int sample = (int)blockIdx.x * 32 + (lane & 31);
+    const bool live = sample < P;
+    const int sp = live ? sample : P - 1;
+    const LkGeoBits b = lk_geo_bits_load(region, sp, h);
+    if (!live) return;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) dec[(size_t)sp * LK_ACT_GEO_A + 32 * i + 8 * (q >> 2) + 4 * h + (q & 3)] = lk_geo_bit(b, i, q) ? 1 : 0;
+}
+__global__ void k_gt_zero(const float* __restrict__ x, int n, uint8_t* __restrict__ ref) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) ref[i] = (x[i] > 0.0f) ? 1 : 0;
+}
+extern "C" int lk_debug_geo_bits(const float* x, int32_t P, int32_t tile_stride, uint32_t* words, uint8_t* dec, uint8_t* ref, void* stream) {
+    LK_REQUIRE(x && words && dec && ref, "lk_debug_geo_bits: null pointer");
+    LK_REQUIRE(P > 0 && P < (1 << 24) && tile_stride >= 1 && tile_stride <= 32, "lk_debug_geo_bits: P must be positive, tile_stride in 1..32");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_geo_bits_pack, dim3(lk_cdiv(P, tile_stride)), dim3(64), 0, st, x, P, tile_stride, words);
+    LK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_geo_bits_read, dim3(lk_cdiv(P, 32)), dim3(64), 0, st, words, P, dec);
+    LK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_gt_zero, dim3(lk_cdiv(P * LK_ACT_GEO_A, 256)), dim3(256), 0, st, x, P * LK_ACT_GEO_A, ref);
+    LK_LAUNCH_CHECK();
+    return LK_OK;
+}
 bool lk_serial_mode() { if (g_serial < 0) g_serial = getenv("LK_SERIAL") != nullptr ? 1 : 0; return g_serial != 0; }
 LkAuxStream& lk_aux_stream() {
     static LkAuxStream s, none;
@@ -488,6 +540,7 @@ int lk_render_bwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
     if (rc != LK_OK) return rc;
     if (d->R == 0) return LK_OK;
     LK_REQUIRE(d->act != nullptr && (d->flags & LK_FLAG_SAVE_ACT), "lk_render_bwd: the forward must run with SAVE_ACT and act");
+    LK_REQUIRE(((uintptr_t)d->act & 15u) == 0, "lk_render_bwd: act must be 16-byte aligned");
     LK_REQUIRE(d->bwd_scratch != nullptr && d->d_depth != nullptr, "lk_render_bwd: bwd_scratch / d_depth missing");
     const uint32_t flags = d->flags;
     const bool color = (flags & LK_FLAG_STAGE_COLOR) != 0, relpos = color && (flags & LK_FLAG_REL_POS);

@@ -378,7 +378,8 @@ __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, in
     const u32x4* __restrict__ FB = reinterpret_cast<const u32x4*>(a.Wfrag) + (GH16 ? FRAGB_U4 : 0);
     const bool want_w = (a.flags & LK_FLAG_GRAD_WEIGHTS) != 0;
     const bool want_p = (a.flags & LK_FLAG_GRAD_RAYS) != 0;
-    const float* act_geo = a.act + (size_t)sp * LK_ACT_GEO_A;
+    // the trunk's relu pattern (lk_kernels.h: LK_ACT_GEO_BITS), one 16-byte load beside the other per-sample operands; dead lanes read sample sp
+    const LkGeoBits gbits = lk_geo_bits_load(lk_geo_bits_region(a.act, a.P), sp, h);
     float4 draw;
     if (a.ml_on) {
         // mapping loop: composite, loss term and composite backward here instead of in k_composite (7-9 us of every iteration); the lane of a
@@ -410,10 +411,15 @@ __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, in
     {
         const float docc = GH16 ? draw.w * SC : draw.w;
         f32x16 dh, dy, dcg, acc1;
-        auto gemm2 = [&](f32x16& acc, const u32x4* fr, const f32x16& x) {        // acc += M^T x over the two 16-k blocks of a 32-wide x
+        auto gemm2 = [&](f32x16& acc, const Piece (&fr)[2], const f32x16& x) {        // acc += M^T x over the two 16-k blocks of a 32-wide x
 #pragma unroll
-            for (int G = 0; G < 2; ++G) acc = PC::mma(PC::load(fr, 1, G, 0, lane), PC::split(x, G), acc);
+            for (int G = 0; G < 2; ++G) acc = PC::mma(fr[G], PC::split(x, G), acc);
         };
+        // U_i^T is fetched one layer AHEAD (the registers the saved relu row took until it became bits, lk_kernels.h: LK_ACT_GEO_BITS), W_i^T at
+        // the top of its layer: d c += U_i^T d h_i starts without a load in front of it, and W_i^T arrives behind those products
+        Piece un[2], uc[2], wc[2];
+#pragma unroll
+        for (int G = 0; G < 2; ++G) un[G] = PC::load(FB + PC::tr(5 + 4), 1, G, 0, lane);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 wo = *reinterpret_cast<const float4*>(W + G_WO + 8 * g + 4 * h);
@@ -422,14 +428,20 @@ __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, in
         dcg = lk_zero16();
 #pragma unroll
         for (int i = 4; i >= 0; --i) {
-            const u32x4* Utr = FB + PC::tr(5 + i);
-            gemm2(dcg, Utr, dh);
-            const f32x16 av = ct_load32(act_geo + i * 32, lane);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) dy[q] = (av[q] > 0.0f) ? dh[q] : 0.0f;
+            for (int G = 0; G < 2; ++G) {
+                uc[G] = un[G];
+                if (i > 0) un[G] = PC::load(FB + PC::tr(5 + i - 1), 1, G, 0, lane);
+                if (i == 3) wc[G] = PC::load(FB + PC::tr(3), 4, G, 3, lane);
+                else if (i != 0) wc[G] = PC::load(FB + PC::tr(i), 1, G, 0, lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);      // the layer's loads are issued here, not where they are used
+            gemm2(dcg, uc, dh);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) dy[q] = lk_geo_bit(gbits, i, q) ? dh[q] : 0.0f;
             if (i == 4 || i == 2 || i == 1) {
                 acc1 = lk_zero16();
-                gemm2(acc1, FB + PC::tr(i), dy);
+                gemm2(acc1, wc, dy);
                 dh = acc1;
             } else if (i == 3) {
                 // layer 3 reads [embedding | h_2]: only the h_2 block of W_3^T d y_3 is needed now.  The three embedding blocks are
@@ -442,7 +454,7 @@ __device__ __forceinline__ void decode_bwd_geo_wave(const LkDecodeBwdArgs& a, in
                     const Piece b = PC::split(dy, G);
 #pragma unroll
                     for (int q = 0; q < NP; ++q) park[(G * NP + q) * 64 + lane] = b.p[q];
-                    acc1 = PC::mma(PC::load(FB + PC::tr(3), 4, G, 3, lane), b, acc1);
+                    acc1 = PC::mma(wc[G], b, acc1);
                 }
                 dh = acc1;
             }

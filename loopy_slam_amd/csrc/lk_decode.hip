@@ -91,11 +91,13 @@ __device__ __forceinline__ f32x16 sincos_embed_tile(const float* __restrict__ B,
 template <int NB, bool SOFTPLUS, bool SA = false>
 __device__ __forceinline__ void layer_finish(f32x16 (&acc)[NB],
                                              const u32x4* __restrict__ UfragB, const float* __restrict__ ubias,
-                                             const LkH8 (&cb)[2], float* __restrict__ save_a, bool live, int lane) {
+                                             const LkH8 (&cb)[2], float* __restrict__ save_a, bool live, int lane,
+                                             LkGeoBits* bits = nullptr, int layer = 0) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {          // acc started from the layer's bias (lk_rowvec_tile)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nb][r] = SOFTPLUS ? lk_softplus100(acc[nb][r]) : fmaxf(acc[nb][r], 0.0f);
+        if (bits) lk_geo_bits_put(*bits, layer, acc[nb]);        // (NB = 1: the geometry trunk) the decision on the value the row holds
         if (save_a) ct_store_rows32(save_a + nb * 32, acc[nb], live, lane);
         lk_add_rowvec<SA>(acc[nb], ubias, nb * 32, lane);
 #pragma unroll
@@ -127,16 +129,23 @@ __device__ __forceinline__ DecSample dec_sample(const LkDecodeArgs& a, int tile,
 }
 
 // ================= geometry decoder (hidden 32, relu): one wave = one 32-sample tile, registers only =================
-template <bool CHECK = false, bool SA = false>
-__device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile, int lane) {      // returns the occupancy of lane & 31's sample
+// Two device functions, chosen once per wave (decode_geo_wave): decode_geo_wave_rows saves the fp32 relu rows beside the relu bits
+// (LkDecodeArgs::geo_rows; lk_kernels.h: LK_ACT_GEO_BITS) and is the chain as it was - a row store per layer, which orders the layer's fc_c
+// loads behind its W loads (a conditional store does so just the same); decode_geo_wave_bits<SAVE> saves the bits alone (1) or nothing (0).
+// One body with the fences and stores behind `if constexpr` was tried: with the row store's address alive beside a layer's sixteen loads
+// the mapper's form spills (168 registers, 5 to 24 spilled words, whichever of the two ways the row address was formed), so the form with
+// rows - which no timed path takes - keeps the placement the compiler gives it.
+template <bool CHECK, bool SA>
+__device__ __forceinline__ float decode_geo_wave_rows(const LkDecodeArgs& a, int tile, int lane) {      // returns the occupancy of lane & 31's sample
     const DecSample d = dec_sample(a, tile, lane);
     const int h = d.h, sp = d.sp;
     const bool live = d.live;
     const float a0 = d.a0, a1 = d.a1, a2 = d.a2;
     const float* __restrict__ W = a.W;
     const u32x4* __restrict__ FB = reinterpret_cast<const u32x4*>(a.Wfrag) + FRAGB_U4;      // fp16 forward fragments
-    const bool save = (a.flags & LK_FLAG_SAVE_ACT) && a.act != nullptr;
-    float* act_geo = save ? a.act + (size_t)sp * LK_ACT_GEO_A : nullptr;
+    float* act_geo = a.act + (size_t)sp * LK_ACT_GEO_A;
+    LkGeoBits gbits = {{0u, 0u, 0u}};
+    LkGeoBits* const gb = &gbits;
     // the 96 embedding units and the interpolated feature are B operands twice / five times: split once
     LkH8 eb[6], cb[2];
     {
@@ -156,20 +165,20 @@ __device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile
     acc[0] = lk_rowvec_tile<SA>(W + G_B0, 0, lane);
 #pragma unroll
     for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load<SA>(FB + FM0_FWDH, 1, G, 0, lane), eb[G], acc[0]);
-    layer_finish<1, false, SA>(acc, FB + FM5_FWDH, W + G_U0 + a64(HG * CF), cb, act_geo, live, lane);
+    layer_finish<1, false, SA>(acc, FB + FM5_FWDH, W + G_U0 + a64(HG * CF), cb, act_geo, live, lane, gb, 0);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(6);
     // layers 1, 2: 32 -> 32
     acc[0] = lk_rowvec_tile<SA>(W + G_B1, 0, lane);
     lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM1_FWDH, 1, 0, 0, hh, 0, lane);
     layer_finish<1, false, SA>(acc, FB + FM6_FWDH, W + G_U0 + G_USTRIDE + a64(HG * CF), cb,
-                           act_geo ? act_geo + 32 : nullptr, live, lane);
+                           act_geo + 32, live, lane, gb, 1);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(7);
     acc[0] = lk_rowvec_tile<SA>(W + G_B2, 0, lane);
     lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM2_FWDH, 1, 0, 0, hh, 0, lane);
     layer_finish<1, false, SA>(acc, FB + FM7_FWDH, W + G_U0 + 2 * G_USTRIDE + a64(HG * CF), cb,
-                           act_geo ? act_geo + 64 : nullptr, live, lane);
+                           act_geo + 64, live, lane, gb, 2);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(8);
     // layer 3 (skip): [e(93) | h(32)] -> 32, packed as [96 | 32]
@@ -178,14 +187,14 @@ __device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile
     for (int G = 0; G < 6; ++G) acc[0] = lk_mma3h(lk_fragh_load<SA>(FB + FM3_FWDH, 1, G, 0, lane), eb[G], acc[0]);
     lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM3_FWDH, 1, 6, 0, hh, 0, lane);
     layer_finish<1, false, SA>(acc, FB + FM8_FWDH, W + G_U0 + 3 * G_USTRIDE + a64(HG * CF), cb,
-                           act_geo ? act_geo + 96 : nullptr, live, lane);
+                           act_geo + 96, live, lane, gb, 3);
     hh = acc[0]; ct_check_range<CHECK>(hh, a.status);
     LK_STAMP(9);
     // layer 4
     acc[0] = lk_rowvec_tile<SA>(W + G_B4, 0, lane);
     lk_gemm_h3<1, 2, (LK_SPLIT_FMA != 0), SA>(acc, FB + FM4_FWDH, 1, 0, 0, hh, 0, lane);
     layer_finish<1, false, SA>(acc, FB + FM9_FWDH, W + G_U0 + 4 * G_USTRIDE + a64(HG * CF), cb,
-                           act_geo ? act_geo + 128 : nullptr, live, lane);
+                           act_geo + 128, live, lane, gb, 4);
     // output 32 -> 1 on the VALU: each half-wave holds 16 of the 32 units of its sample
     float part = 0.0f;
 #pragma unroll
@@ -196,8 +205,122 @@ __device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile
     }
     part += __shfl_xor(part, 32);
     if (live && h == 0) a.raw[(size_t)d.sample * 4 + 3] = part + W[G_BO];
+    lk_geo_bits_store(lk_geo_bits_region(a.act, a.P), d.sample, h, gbits, live);
     LK_STAMP(10);
     return part + W[G_BO];
+}
+// The forms WITHOUT row stores (SAVE = 0, 1): nothing orders a layer's loads any more, so they are placed by hand - a layer's W fragments,
+// bias, fc_c fragments and fc_c bias are issued together, in front of its first product, and the scheduling fences keep the compiler from
+// sinking them back to their uses (or from hoisting every later layer's to the top: 196 registers).  Same products in the same order as
+// decode_geo_wave_rows: bit-identical.
+// (the hidden products are written out as lk_mma3h(fragment, lk_split_cth(h, G), acc): that IS lk_gemm_h3<1, 2, LK_SPLIT_FMA> of
+// decode_geo_wave_rows - lk_split_cth's default cut is the LK_SPLIT_FMA one - with the cut moved in front of the fence)
+#define LK_GEO_FENCE() __builtin_amdgcn_sched_barrier(0)
+template <bool CHECK, bool SA, int SAVE>
+__device__ __forceinline__ float decode_geo_wave_bits(const LkDecodeArgs& a, int tile, int lane) {
+    static_assert(SAVE == 0 || SAVE == 1, "the forms without row stores");
+    const DecSample d = dec_sample(a, tile, lane);
+    const int h = d.h, sp = d.sp;
+    const float a0 = d.a0, a1 = d.a1, a2 = d.a2;
+    const float* __restrict__ W = a.W;
+    const u32x4* __restrict__ FB = reinterpret_cast<const u32x4*>(a.Wfrag) + FRAGB_U4;      // fp16 forward fragments
+    constexpr int WM[5] = {FM0_FWDH, FM1_FWDH, FM2_FWDH, FM3_FWDH, FM4_FWDH}, UM[5] = {FM5_FWDH, FM6_FWDH, FM7_FWDH, FM8_FWDH, FM9_FWDH};
+    constexpr int BO[5] = {G_B0, G_B1, G_B2, G_B3, G_B4};
+    LkGeoBits gbits = {{0u, 0u, 0u}};
+    LkH8 eb[6], cb[2];
+    {
+        const f32x16 e0 = geo_embed_tile(W + G_EB, 0, a0, a1, a2, lane);
+        eb[0] = lk_split_cth(e0, 0); eb[1] = lk_split_cth(e0, 1);
+        const f32x16 e1 = geo_embed_tile(W + G_EB, 1, a0, a1, a2, lane);
+        eb[2] = lk_split_cth(e1, 0); eb[3] = lk_split_cth(e1, 1);
+        const f32x16 e2 = geo_embed_tile(W + G_EB, 2, a0, a1, a2, lane);
+        eb[4] = lk_split_cth(e2, 0); eb[5] = lk_split_cth(e2, 1);
+        const f32x16 cg = ct_load_rows32(a.c_geo + (size_t)sp * LK_C, true, lane);
+        ct_check_range<CHECK>(cg, a.status);
+        cb[0] = lk_split_cth(cg, 0); cb[1] = lk_split_cth(cg, 1);
+    }
+    LK_STAMPW(5);
+    f32x16 acc, hh = lk_zero16();
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const bool emb = (i == 0 || i == 3);
+        LK_GEO_FENCE();
+        // every operand of the layer in flight at once (layers 0 and 3: the hidden / fc_c blocks behind the first embedding products, whose
+        // fragment registers they take over)
+        LkH8 we[6], wh[2], u[2], hb[2];
+        f32x16 ub;
+        if (i != 0) { hb[0] = lk_split_cth(hh, 0); hb[1] = lk_split_cth(hh, 1); }       // (cut while the loads fly)
+        acc = lk_rowvec_tile<SA>(W + BO[i], 0, lane);
+        if (emb) {
+#pragma unroll
+            for (int G = 0; G < 6; ++G) we[G] = lk_fragh_load<SA>(FB + WM[i], 1, G, 0, lane);
+            LK_GEO_FENCE();
+#pragma unroll
+            for (int G = 0; G < 4; ++G) acc = lk_mma3h(we[G], eb[G], acc);
+            LK_GEO_FENCE();
+        }
+        if (i != 0) {
+#pragma unroll
+            for (int G = 0; G < 2; ++G) wh[G] = lk_fragh_load<SA>(FB + WM[i], 1, (i == 3 ? 6 : 0) + G, 0, lane);
+        }
+#pragma unroll
+        for (int G = 0; G < 2; ++G) u[G] = lk_fragh_load<SA>(FB + UM[i], 1, G, 0, lane);
+        if (i != 3) ub = lk_rowvec_tile<SA>(W + G_U0 + i * G_USTRIDE + a64(HG * CF), 0, lane);
+        LK_GEO_FENCE();
+        if (emb) {
+#pragma unroll
+            for (int G = 4; G < 6; ++G) acc = lk_mma3h(we[G], eb[G], acc);
+        }
+        if (i == 3) {       // (layer 3 holds eight W blocks and h_2: its fc_c bias takes the registers of the last embedding blocks)
+            LK_GEO_FENCE();
+            ub = lk_rowvec_tile<SA>(W + G_U0 + i * G_USTRIDE + a64(HG * CF), 0, lane);
+            LK_GEO_FENCE();
+        }
+        if (i != 0) {
+#pragma unroll
+            for (int G = 0; G < 2; ++G) acc = lk_mma3h(wh[G], hb[G], acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+        if (SAVE) lk_geo_bits_put(gbits, i, acc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += ub[r];
+#pragma unroll
+        for (int G = 0; G < 2; ++G) acc = lk_mma3h(u[G], cb[G], acc);
+        LK_STAMP(6 + i);
+        hh = acc;
+        if (i < 4) ct_check_range<CHECK>(hh, a.status);
+    }
+    // output 32 -> 1 on the VALU: each half-wave holds 16 of the 32 units of its sample
+    float part = 0.0f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 wo = *reinterpret_cast<const float4*>(W + G_WO + 8 * g + 4 * h);
+        part = fmaf(wo.x, acc[4 * g], part); part = fmaf(wo.y, acc[4 * g + 1], part);
+        part = fmaf(wo.z, acc[4 * g + 2], part); part = fmaf(wo.w, acc[4 * g + 3], part);
+    }
+    part += __shfl_xor(part, 32);
+    // the sample's index and liveness are derived AGAIN from the lane (opaque: not the values of the prologue) - one register instead of five
+    // lives through the layers
+    const int ln = lk_opaque(lane);
+    const int ts = a.tile_stride ? a.tile_stride : 32;
+    const int smp = tile * ts + (ln & 31);
+    const bool lv = smp < a.P && (ln & 31) < ts;
+    if (lv && (ln >> 5) == 0) a.raw[(size_t)smp * 4 + 3] = part + W[G_BO];
+    if (SAVE) lk_geo_bits_store(lk_geo_bits_region(a.act, a.P), smp, ln >> 5, gbits, lv);
+    LK_STAMP(10);
+    return part + W[G_BO];
+}
+#undef LK_GEO_FENCE
+template <bool CHECK = false, bool SA = false>
+__device__ __forceinline__ float decode_geo_wave(const LkDecodeArgs& a, int tile, int lane) {
+    if (!((a.flags & LK_FLAG_SAVE_ACT) && a.act != nullptr)) return decode_geo_wave_bits<CHECK, SA, 0>(a, tile, lane);
+    if (a.geo_rows) return decode_geo_wave_rows<CHECK, SA>(a, tile, lane);
+    // The bits-only form - the one the frame loops run - takes scalar-base fragment loads (lk_common.h: lk_sbase) whatever the caller's SA:
+    // with a layer's sixteen loads in flight at once their 64-bit vector addresses are what k_decode_fwd<false, false> has no registers
+    // for (caller's plain addressing: 168 registers and one spilled word; scalar bases: 166, no spill).  The two forms beside it keep the
+    // caller's addressing: with scalar bases in all three the kernel spills 21 words.
+    return decode_geo_wave_bits<CHECK, (LK_FRAG_SADDR != 0), 1>(a, tile, lane);
 }
 
 // The same decoder with its operands in LDS (the tracker's fused launch, k_relpos_decode_fwd: one tile per compute unit, and the geometry wave's
@@ -230,15 +353,15 @@ __device__ __forceinline__ void lk_geo_stage(const LkDecodeArgs& a, int w, int l
         s_gb[j][u] = a.W[j < 5 ? b_off[j] + u : G_U0 + (j - 5) * G_USTRIDE + a64(HG * CF) + u];
     }
 }
-template <bool CHECK = false>
-__device__ __forceinline__ float decode_geo_wave_lds(const LkDecodeArgs& a, int tile, int lane, const u32x4* __restrict__ s_gw, const float (*s_gb)[32]) {
+template <bool CHECK, int SAVE>
+__device__ __forceinline__ float decode_geo_wave_lds_form(const LkDecodeArgs& a, int tile, int lane, const u32x4* __restrict__ s_gw, const float (*s_gb)[32]) {
     const DecSample d = dec_sample(a, tile, lane);
     const int h = d.h, sp = d.sp;
     const bool live = d.live;
     const float a0 = d.a0, a1 = d.a1, a2 = d.a2;
     const float* __restrict__ W = a.W;
-    const bool save = (a.flags & LK_FLAG_SAVE_ACT) && a.act != nullptr;
-    float* act_geo = save ? a.act + (size_t)sp * LK_ACT_GEO_A : nullptr;
+    float* act_geo = SAVE == 2 ? a.act + (size_t)sp * LK_ACT_GEO_A : nullptr;
+    LkGeoBits gbits = {{0u, 0u, 0u}};
     constexpr int WB[5] = {0, 8, 12, 16, 26}, UB[5] = {6, 10, 14, 24, 28};      // first block of W_i / U_i in s_gw
     auto frag = [&](int block) {
         LkH8 f;
@@ -282,9 +405,10 @@ __device__ __forceinline__ float decode_geo_wave_lds(const LkDecodeArgs& a, int 
 #pragma unroll
             for (int G = 0; G < 2; ++G) acc = lk_mma3h(frag(WB[i] + G), lk_split_cth(hh, G), acc);
         }
-        // epilogue: relu, saved row, + u_i, + U_i c
+        // epilogue: relu, its saved bits (and row), + u_i, + U_i c
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+        if (SAVE) lk_geo_bits_put(gbits, i, acc);
         if (act_geo) ct_store_rows32(act_geo + 32 * i, acc, live, lane);
         {
             const f32x16 ub = bias(5 + i);
@@ -307,7 +431,13 @@ __device__ __forceinline__ float decode_geo_wave_lds(const LkDecodeArgs& a, int 
     }
     part += __shfl_xor(part, 32);
     if (live && h == 0) a.raw[(size_t)d.sample * 4 + 3] = part + W[G_BO];
+    if (SAVE) lk_geo_bits_store(lk_geo_bits_region(a.act, a.P), d.sample, h, gbits, live);
     return part + W[G_BO];
+}
+template <bool CHECK = false>
+__device__ __forceinline__ float decode_geo_wave_lds(const LkDecodeArgs& a, int tile, int lane, const u32x4* __restrict__ s_gw, const float (*s_gb)[32]) {
+    if (!((a.flags & LK_FLAG_SAVE_ACT) && a.act != nullptr)) return decode_geo_wave_lds_form<CHECK, 0>(a, tile, lane, s_gw, s_gb);
+    return a.geo_rows ? decode_geo_wave_lds_form<CHECK, 2>(a, tile, lane, s_gw, s_gb) : decode_geo_wave_lds_form<CHECK, 1>(a, tile, lane, s_gw, s_gb);
 }
 
 // ================= colour decoder (hidden 128, softplus beta=100): FOUR waves = one 32-sample tile =================
@@ -577,7 +707,10 @@ __device__ __forceinline__ void decode_col_wg(const LkDecodeArgs& a, int tile, i
 // decoder (4 independent tiles per workgroup) and come FIRST in the grid.  raw[:, 0:3] and raw[:, 3] are written by the two roles separately;
 // in the geometry stage there are no colour blocks and raw[:, 0:3] is zero-filled by the geometry wave.
 template <bool DEEP, bool CHECK = false>
-__global__ __launch_bounds__(256, 2) void k_decode_fwd(LkDecodeArgs a, int n_col_blocks) {
+// launch bound: the mapper's form <false, false> is held to the 168 registers of THREE workgroups per compute unit by the compiler itself (with
+// room for 256 it lets the hand-placed loads of the geometry role take 208; at the bound: 166, no spill - tests/test_product_hygiene.py); the
+// deep and the checked forms keep their two
+__global__ __launch_bounds__(256, (DEEP || CHECK) ? 2 : 3) void k_decode_fwd(LkDecodeArgs a, int n_col_blocks) {
     __shared__ u32x4 s_x[2][16 * 64];
     __shared__ float s_o[4][3 * 32];
     __shared__ float s_bias[10][128];
@@ -592,7 +725,7 @@ __global__ __launch_bounds__(256, 2) void k_decode_fwd(LkDecodeArgs a, int n_col
         decode_col_wg<DEEP, false, CHECK>(a, bid, w, lane, s_x, s_o, s_bias);
         return;
     }
-    const int tile = (bid - n_col_blocks) * 4 + w;
+    const int tile = lk_uniform((bid - n_col_blocks) * 4 + w);      // (a scalar: derived from the wave's index it would sit in a vector register through the whole chain)
     if (tile * 32 >= P_live) return;
     (void)decode_geo_wave<CHECK>(a, tile, lane);
     if (n_col_blocks == 0) {

@@ -85,6 +85,8 @@ struct LkDecodeArgs {
     int tile_stride;                              // 0 = 32; k_relpos_decode_fwd with the composite inside: (32 / S) S - a tile holds whole rays,
                                                   // its lanes >= tile_stride idle
     unsigned* status;                             // LK_FLAG_CHECK_RANGE: lk_status_dev(), else NULL (no operand checks)
+    int geo_rows;                                 // SAVE_ACT: 1 = the geometry trunk's fp32 relu rows are saved beside its relu bits (a backward with
+                                                  // LK_FLAG_GRAD_GEO_DECODER may follow: k_geo_wgrad reads them), 0 = the bits alone (the frame loops)
 };
 
 // relative-position neighbour MLP (colour features, Replica config)
@@ -357,7 +359,8 @@ enum { LK_SKIP_COMPOSITE = 1, LK_SKIP_COMPOSITE_BWD = 2, LK_SKIP_RAYS_BWD = 4, L
        LK_PRESAMPLED = 64 /* fwd: z / nbr_idx / nbr_w / nbr_count are given (lk_presample), only interpolate */,
        LK_SKIP_AFF_REDUCE = 256 /* bwd: the caller sums the per-tile d affine partials itself (k_track_final's exposure workgroup) */,
        LK_COMPOSITE_IN_BWD = 512 /* mapping loop (MAPPER_LOSS): fwd launches no composite; bwd forms d raw in the prologue of k_decode_bwd (LkBwdExtra::loss_rows) */,
-       LK_FUSE_SMALL = 128 /* tracker-sized batches: rel-pos MLP + decoders in one launch (fwd), rel-pos backward + interpolation backward in one (bwd) */ };
+       LK_FUSE_SMALL = 128 /* tracker-sized batches: rel-pos MLP + decoders in one launch (fwd), rel-pos backward + interpolation backward in one (bwd) */,
+       LK_GEO_BITS_ONLY = 1024 /* fwd: no backward with LK_FLAG_GRAD_GEO_DECODER follows - the geometry trunk saves its relu bits, not its rows (LkDecodeArgs::geo_rows) */ };
 // cnt: the batch holds n iterations of P_iter samples each (n <= LK_SEG_BATCH); their rows are counted per point on the way
 struct LkPresampleCount { int P_iter; int32_t* seg_rank; const int32_t* live_rays; const int32_t* key_of; };
 int lk_presample(const lk_render_desc* d, hipStream_t st, const LkPresampleCount* cnt = nullptr);
@@ -414,7 +417,8 @@ int lk_launch_relpos_decode_fwd(const LkRelposArgs& ra, const LkDecodeArgs& a, h
 int lk_launch_relpos_interp_bwd(const LkRelposBwdArgs& rb, const LkInterpBwdArgs& ib, hipStream_t st, bool h16);  // k_relpos_bwd + k_interp_bwd in one launch
 
 // activation scratch layout (floats per sample), SAVE_ACT
-//   [P][160] geometry a_i | [P][320] colour softplus'(z_i) as unorm16 pairs | [P][640] colour h_i | [P][40] colour embedding  (i = 0..4)
+//   [P][160] geometry a_i | [P][320] colour softplus'(z_i) as unorm16 pairs | [P][640] colour h_i | [P][40] colour embedding | [P][8] geometry relu bits
+//   (i = 0..4; the geometry a_i rows only behind LkDecodeArgs::geo_rows, the words are the region's either way)
 //   a_i = act(z_i), z_i = W_i x_i + b_i, h_i = a_i + fc_c_i(c).  The colour trunk's backward needs a_i only for d y_i = d h_i softplus'(z_i):
 //   the forward stores that factor in 16 bits (lk_pack_unorm16; round 5 stored the a_i rows, 64 MB per 5 000-ray batch written and read back)
 #define LK_ACT_GEO_A (5 * 32)
@@ -427,6 +431,38 @@ int lk_launch_relpos_interp_bwd(const LkRelposBwdArgs& rb, const LkInterpBwdArgs
 #define LK_ACT_COL_H (5 * 128)
 #define LK_ACT_COL_E 40       // colour Fourier embedding (input of layers 0 and 3)
 #define LK_ACT_FLOATS_PER_SAMPLE (LK_ACT_GEO_A + LK_ACT_COL_A + LK_ACT_COL_H + LK_ACT_COL_E)
+// Behind those four regions: [P][8] words, the geometry trunk's relu pattern.  The decoder backward needs of a_i only the decision a_i > 0
+// (d y_i = d h_i where it holds, else 0): 160 bits per sample instead of 160 floats.  The rows themselves are read by k_geo_wgrad alone
+// (LK_FLAG_GRAD_GEO_DECODER) and written only where such a backward can follow (LkDecodeArgs::geo_rows); the bits are written by every
+// SAVE_ACT forward and read by every decoder backward.  Addressed by SAMPLE - the tracker's fused forward walks tiles of (32 / S) S samples,
+// the backward tiles of 32: words [4 h, 4 h + 4) of a sample belong to half-wave h (the CT tile's lane = sample + 32 h), which holds the
+// units 8 g + 4 h + t of a layer in its registers q = 4 g + t: word 0 = layers 0 | 1 << 16, word 1 = layers 2 | 3 << 16, word 2 = layer 4,
+// word 3 = 0; bit q of a layer's 16 = (a_i[8 g + 4 h + t] > 0.0f), the floating compare on the value the row would hold.
+#define LK_ACT_GEO_BITS 8
+#define LK_ACT_WORDS_PER_SAMPLE (LK_ACT_FLOATS_PER_SAMPLE + LK_ACT_GEO_BITS)
+struct LkGeoBits { unsigned w[3]; };
+__device__ __forceinline__ void lk_geo_bits_put(LkGeoBits& b, int layer, const f32x16& a) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int q = 15; q >= 0; --q) m = (m << 1) | ((a[q] > 0.0f) ? 1u : 0u);      // (shifted in from the top: no register of bit constants)
+    // (opaque: the word is formed HERE.  It is needed only by the store behind the last layer, and the compiler otherwise sinks the sixteen
+    // compares down to it and keeps - spills - every layer's relu tile until then)
+    m = (unsigned)lk_opaque((int)m);
+    b.w[layer >> 1] |= m << (16 * (layer & 1));
+}
+__device__ __forceinline__ bool lk_geo_bit(const LkGeoBits& b, int layer, int q) { return ((b.w[layer >> 1] >> (16 * (layer & 1) + q)) & 1u) != 0u; }
+__device__ __forceinline__ unsigned* lk_geo_bits_region(const float* act, int P) {
+    return reinterpret_cast<unsigned*>(const_cast<float*>(act) + (size_t)P * LK_ACT_FLOATS_PER_SAMPLE);
+}
+__device__ __forceinline__ void lk_geo_bits_store(unsigned* region, int sample, int h, const LkGeoBits& b, bool live) {
+    if (live) *reinterpret_cast<u32x4*>(region + (size_t)sample * LK_ACT_GEO_BITS + 4 * h) = u32x4{b.w[0], b.w[1], b.w[2], 0u};
+}
+__device__ __forceinline__ LkGeoBits lk_geo_bits_load(const unsigned* region, int sample, int h) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(region + (size_t)sample * LK_ACT_GEO_BITS + 4 * h);
+    LkGeoBits b;
+    b.w[0] = v[0]; b.w[1] = v[1]; b.w[2] = v[2];
+    return b;
+}
 // The colour trunk's saved activations (a_i, h_i) and its d h_i rows are LAYER-MAJOR, [layer][P][128]: a job of the weight-gradient
 // reduction then streams one contiguous [P][128] array (512-byte pieces of 2.5-KB rows cost it a third of its bandwidth), and the 32
 // samples x 128 bytes a wave of the decoders stores per layer sit 512 bytes apart instead of 2 560.

@@ -419,7 +419,7 @@ extern "C" int lk_track_frame(const lk_track_desc* d, void* stream_) {
         }
         // (pass 1 of the loss rides in the forward's launch where it can: comp_tiles = its number of partial pairs)
         int comp_tiles = 0;
-        int rc = lk_render_fwd_impl(&rd, st, fused ? (LK_SKIP_COMPOSITE | LK_FUSE_SMALL) : 0, nullptr, nullptr, (prologue && it > 0) ? &pa : nullptr,
+        int rc = lk_render_fwd_impl(&rd, st, (fused ? (LK_SKIP_COMPOSITE | LK_FUSE_SMALL) : 0) | LK_GEO_BITS_ONLY, nullptr, nullptr, (prologue && it > 0) ? &pa : nullptr,
                                     fused ? &la : nullptr, &comp_tiles);
         if (rc != LK_OK) return rc;
         const int n_part = comp_tiles > 0 ? comp_tiles : n_lp;
@@ -754,7 +754,7 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
             if (comp_bwd) { if (sum_lo < 0) sum_lo = it; sum_hi = it + 1; }
             // exposure variant: the composite runs inside the loss kernel below (one launch instead of two)
             rc = lk_render_fwd_impl(&rd, st, (xit ? LK_SKIP_COMPOSITE : LK_FUSE_COMPOSITE_BWD) | (pre ? (LK_LOSS_PREZEROED | LK_PRESAMPLED) : 0) |
-                                    (sort_ahead ? LK_SEG_SORTED : 0) | (comp_bwd ? LK_COMPOSITE_IN_BWD : 0), live,
+                                    (sort_ahead ? LK_SEG_SORTED : 0) | (comp_bwd ? LK_COMPOSITE_IN_BWD : 0) | (train_geo ? 0 : LK_GEO_BITS_ONLY), live,
                                     (repack_pending || stepped_pending || split_repack) ? &rr : nullptr, nullptr, nullptr, nullptr, join_side);
             repack_pending = false; stepped_pending = false; split_pending = 0;
             if (rc != LK_OK) return rc;
