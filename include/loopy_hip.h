@@ -835,6 +835,21 @@ int lk_debug_occupancy(int32_t out[5]);
  * microseconds (0 = off, the default) - a missing ordering between the side stream and the launch stream then fails deterministically
  * instead of by timing (tests/test_split_step_order.py).  Results must not depend on it. */
 int lk_debug_side_delay(int32_t us);
+/* Test hook, the general form (lk_debug_side_delay(us) is site LK_DELAY_WGRAD): one delay site per stream of the library.  A site that is
+ * on puts the same spinning kernel (one wave) of `us` microseconds at every place listed for it; us = 0 switches the site off.  The three
+ * side-stream sites make that stream LATE (a missing join shows as a read before the write), LK_DELAY_LAUNCH makes the caller's stream
+ * late behind every fork, so the library's streams run AHEAD of it (a buffer reused too early shows as a write before the last read).
+ * us outside 0 .. LK_DELAY_MAX_US and unknown sites are refused with LK_ERR_ARG and change nothing.  In one-stream mode (lk_set_serial)
+ * no site launches anything; with every site off the launches of every call are exactly those without the hook.  Results must not
+ * depend on any site (tests/test_stream_order.py holds whole calls to equal bits). */
+#define LK_DELAY_WGRAD  0  /* weight-gradient stream, in front of the forked k_wgrad of a backward */
+#define LK_DELAY_SORT   1  /* weight-gradient stream, in front of the forked counting sort of a standalone lk_render_bwd */
+#define LK_DELAY_AHEAD  2  /* look-ahead stream of lk_map_frame, in front of every chunk's search and once more between its search and its sorts */
+#define LK_DELAY_LAUNCH 3  /* the caller's stream, right behind every fork: the weight-gradient fork and the sort fork of a backward, and every
+                              look-ahead chunk that lk_map_frame enqueues */
+#define LK_DELAY_SITES  4
+#define LK_DELAY_MAX_US 2000
+int lk_debug_stream_delay(int32_t site, int32_t us);
 /* Test hook: the fp16 two-piece cut of the forward kernels (hi = rtz_f16(x), lo = rtz_f16(x - hi)) over n values (n even, device
  * pointers): hi / lo [n/2] = the packed pieces of the pairs (x[2i], x[2i+1]) in the production form, hi_ref / lo_ref [n/2] = the same
  * from the convert-and-subtract form it replaced (tests/test_split_forms.py: the two must agree bit for bit). */

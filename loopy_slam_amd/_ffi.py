@@ -196,6 +196,7 @@ class LoopyLib:
             ('lk_streams_init', [], C.c_int),
             ('lk_debug_occupancy', [C.POINTER(C.c_int32)], C.c_int),
             ('lk_debug_side_delay', [C.c_int32], C.c_int),
+            ('lk_debug_stream_delay', [C.c_int32, C.c_int32], C.c_int),
             ('lk_debug_split_forms', [_fp, C.c_int32, _fp, _fp, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_debug_geo_bits', [_fp, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_weights_repack_checked', [_fp, _fp, C.c_void_p], C.c_int),

@@ -368,12 +368,26 @@ static int lk_wait_side_join(hipStream_t st) {
 // Test hook (tests/test_split_step_order.py): every weight-gradient launch that is forked onto the side stream is preceded there by a kernel
 // that spins for `us` microseconds - the side stream then trails the launch stream by that much, which turns any missing ordering between
 // the two (round 5: iteration it's k_wgrad against iteration it + 1's c_col writes) from a timing accident into a deterministic failure.
-namespace { int g_side_delay_us = 0; }
+// lk_debug_stream_delay generalises it to one site per stream of the library (LK_DELAY_*, tests/test_stream_order.py): the three side-stream
+// sites make that stream late (a missing join: read before write), LK_DELAY_LAUNCH makes the LAUNCH stream late behind every fork, so the
+// other streams run ahead of it (a reuse hazard: write before the previous read has finished).  Every site sits inside the branch that
+// forks, so one-stream mode launches nothing, and with every site off the enqueue sequence is the one without the hook.
+namespace { int g_delay_us[LK_DELAY_SITES] = {0, 0, 0, 0}; }
 __global__ void k_spin_us(long long ticks) {
     const long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
-extern "C" int lk_debug_side_delay(int32_t us) { g_side_delay_us = us > 0 ? us : 0; return LK_OK; }
+void lk_debug_delay(int site, hipStream_t st) {
+    if (g_delay_us[site] > 0) hipLaunchKernelGGL(k_spin_us, dim3(1), dim3(64), 0, st, (long long)g_delay_us[site] * 100);   // wall_clock64: 100 MHz
+}
+extern "C" int lk_debug_stream_delay(int32_t site, int32_t us) {
+    // (the bound: a typo must not park a wave on the chip for seconds)
+    LK_REQUIRE(site >= 0 && site < LK_DELAY_SITES, "lk_debug_stream_delay: unknown site");
+    LK_REQUIRE(us >= 0 && us <= LK_DELAY_MAX_US, "lk_debug_stream_delay: us must be in 0 .. 2000");
+    g_delay_us[site] = us;
+    return LK_OK;
+}
+extern "C" int lk_debug_side_delay(int32_t us) { return lk_debug_stream_delay(LK_DELAY_WGRAD, us > 0 ? us : 0); }
 extern "C" int lk_set_serial(int32_t on) { g_serial = on ? 1 : 0; return LK_OK; }
 // Creates the library's two streams NOW instead of at their first use.  The runtime hands its few hardware queues to streams as they are
 // created: a process that first creates dozens of other streams (torch's stream pool comes into being with the first collective of a
@@ -516,11 +530,15 @@ static int seg_sort_async(const lk_render_desc* d, int P, bool counted, hipStrea
     seg_args(d, P, fs);
     SideStream& ss = side_stream();
     if (!ss.ok) return lk_launch_seg_sort(fs, counted, st);
-    (void)hipEventRecord(ss.fork0, st);
-    (void)hipStreamWaitEvent(ss.st, ss.fork0, 0);
+    // (the gather's order behind the sort hangs on these events: a failed record is an error, not a lost overlap)
+    LK_HIP_TRY(hipEventRecord(ss.fork0, st));
+    LK_HIP_TRY(hipStreamWaitEvent(ss.st, ss.fork0, 0));
+    lk_debug_delay(LK_DELAY_LAUNCH, st);
+    lk_debug_delay(LK_DELAY_SORT, ss.st);
     const int rc = lk_launch_seg_sort(fs, counted, ss.st);
-    (void)hipEventRecord(ss.link, ss.st);
-    return rc;
+    if (rc != LK_OK) return rc;
+    LK_HIP_TRY(hipEventRecord(ss.link, ss.st));
+    return LK_OK;
 }
 
 extern "C" int lk_render_bwd(const lk_render_desc* d, void* stream_) {
@@ -632,8 +650,9 @@ int lk_render_bwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
     if (ex && ex->split_done) *ex->split_done = split ? 1 : 0;
     hipStream_t wst = st;                      // stream of the weight-gradient launches
     if (forked) {
-        (void)hipEventRecord(ss.fork, st);
-        (void)hipStreamWaitEvent(ss.st, ss.fork, 0);
+        LK_HIP_TRY(hipEventRecord(ss.fork, st));
+        LK_HIP_TRY(hipStreamWaitEvent(ss.st, ss.fork, 0));
+        lk_debug_delay(LK_DELAY_LAUNCH, st);
         wst = ss.st;
     }
     if (gwf && color) {
@@ -678,7 +697,7 @@ int lk_render_bwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
         wa.n_jobs = nj; wa.chunk = 0; wa.part = S0 + L.wg_part;
         wa.h16 = (flags & LK_FLAG_UNIT_LOSS_GRADS) && !gr ? 1 : 0;
         wa.live_rays = ex ? ex->live_rays : nullptr; wa.S = d->S; wa.dscale = ex ? ex->dscale : nullptr;
-        if (forked && g_side_delay_us > 0) hipLaunchKernelGGL(k_spin_us, dim3(1), dim3(64), 0, wst, (long long)g_side_delay_us * 100);   // wall_clock64: 100 MHz
+        if (forked) lk_debug_delay(LK_DELAY_WGRAD, wst);
         lk_launch_wgrad(wa, P, wst, defer ? &wdef : nullptr);
         if (split) {
             // the trunk's half of the step, right behind its weight gradients on their stream: tile sums + fc_c products with the Adam rider
@@ -709,7 +728,7 @@ int lk_render_bwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
         // the weight-gradient stream waits for the rel-pos backward only where it consumes its rows (the unfused linear1 / linear2 jobs below): in
         // the fused form nothing on that stream depends on it, and the event record on the caller's stream is a 6-7 us bubble between the rel-pos
         // backward and the gather of every 'color' iteration (tools/trace_window.py)
-        if (forked && !lk_relpos_fused(flags)) { (void)hipEventRecord(ss.mid, st); (void)hipStreamWaitEvent(wst, ss.mid, 0); }
+        if (forked && !lk_relpos_fused(flags)) { LK_HIP_TRY(hipEventRecord(ss.mid, st)); LK_HIP_TRY(hipStreamWaitEvent(wst, ss.mid, 0)); }
         // (the fused kernel - kept in the embedding-only mode, where its linear1 tiles go unused - leaves one partial row per workgroup)
         if (gw && !defer) lk_launch_reduce_partials(S0 + L.part_br, lk_relpos_fused(flags) ? lk_relpos_bwd_parts(P) : lk_cdiv(lk_cdiv(P, 4), 4), 32,
                                                     d->g_weights + R_EB, st);
@@ -719,7 +738,7 @@ int lk_render_bwd_impl(const lk_render_desc* d, hipStream_t st, unsigned skip, c
         fs.dc_geo = S0 + L.dc_geo; fs.dc_col = (color && !relpos) ? S0 + L.dc_col : nullptr; fs.dfeat = relpos ? S0 + L.dfeat : nullptr;
         fs.g_geo_feats = d->g_geo_feats; fs.g_col_feats = d->g_col_feats;
         if (ex && ex->seg_list) { fs.seg_list = ex->seg_list; fs.seg_total = ex->seg_total; }      // sorted ahead of the loop (lk_map_frame)
-        else if (ss.ok) (void)hipStreamWaitEvent(st, ss.link, 0);
+        else if (ss.ok) LK_HIP_TRY(hipStreamWaitEvent(st, ss.link, 0));
         fs.act_flag = ex ? ex->act_flag : nullptr;
         if (bg_rides) { fs.red_part = S0 + L.part_bg; fs.red_n = lk_cdiv(lk_cdiv(P, 32), 4); fs.red_width = 288; fs.red_out = d->g_weights + G_EB; }
         if (dw2_rides) {       // linear2 of the rel-pos MLP: k_dw2_hbar's blocks in front of the gather's (without feature gradients: a launch of its own, below)

@@ -366,6 +366,7 @@ struct LkPresampleCount { int P_iter; int32_t* seg_rank; const int32_t* live_ray
 int lk_presample(const lk_render_desc* d, hipStream_t st, const LkPresampleCount* cnt = nullptr);
 int lk_wait_rows_event(hipStream_t st);                     // lk_map_wait_rows
 bool lk_serial_mode();                                      // LK_SERIAL / lk_set_serial: one stream only
+void lk_debug_delay(int site, hipStream_t st);              // lk_debug_stream_delay: the spin kernel of `site` on st if that site is on (callers: forked branches only)
 // library-owned third stream (lk_map_frame's search ahead of the loop; small independent launches of the backward)
 #define LK_PRE_CHUNKS 16
 struct LkAuxStream { hipStream_t st = nullptr; hipEvent_t e0 = nullptr; hipEvent_t ev[LK_PRE_CHUNKS] = {}; hipEvent_t e1 = nullptr, e2 = nullptr; bool ok = false; };

@@ -497,7 +497,7 @@ extern "C" int lk_track_frame(const lk_track_desc* d, void* stream_) {
 // ------------------------------------------------------------------ lk_map_frame
 // Start of an optimize_map call (or of a segment of one): join the look-ahead stream, then assemble the batches of every iteration.
 // Neither step reads the optimised rows, the map or the decoders - lk_map_prepare can run it before the caller knows its row list.
-static void map_join_and_pregather(const lk_map_desc* d, const MapWork& wk, int R, const lk_exposure_desc* xd, hipStream_t st) {
+static int map_join_and_pregather(const lk_map_desc* d, const MapWork& wk, int R, const lk_exposure_desc* xd, hipStream_t st) {
     float* W0 = d->work;
     {
         // A call that starts an optimize_map call joins the look-ahead stream first: an earlier call that stopped before its last enqueued
@@ -505,7 +505,7 @@ static void map_join_and_pregather(const lk_map_desc* d, const MapWork& wk, int 
         // sorting there - reading the `work` buffer this call's k_pregather overwrites and holding the index's row counters mid-sort.
         // With an idle look-ahead stream the wait is satisfied at once.
         PreStream& pj = pre_stream();
-        if (pj.ok) { (void)hipEventRecord(pj.e1, pj.st); (void)hipStreamWaitEvent(st, pj.e1, 0); }
+        if (pj.ok) { LK_HIP_TRY(hipEventRecord(pj.e1, pj.st)); LK_HIP_TRY(hipStreamWaitEvent(st, pj.e1, 0)); }
     }
     {
         // pixels, rays, colours, radii and the inside mask of EVERY iteration of this optimize_map call in one launch; it also
@@ -523,6 +523,7 @@ static void map_join_and_pregather(const lk_map_desc* d, const MapWork& wk, int 
         if (R <= LK_MASK_REG_MAX) hipLaunchKernelGGL(k_pregather<LK_MASK_VPT>, dim3(d->iters), dim3(1024), 0, st, pa);
         else hipLaunchKernelGGL(k_pregather<LK_LOOP_MAX_R / 1024>, dim3(d->iters), dim3(1024), 0, st, pa);
     }
+    return LK_OK;
 }
 // The batch assembly of an optimize_map call (or of its first segment) ahead of the call itself: d needs the batch inputs (stacks, frame_id,
 // rnd, window, intrinsics), render.R / S / r2_ray, work, iters, log and exposure - NOT rows, the optimiser buffers or the gradient buffers.
@@ -535,7 +536,8 @@ extern "C" int lk_map_prepare(const lk_map_desc* d, void* stream_) {
     LK_REQUIRE(d->depth_stack && d->color_stack && d->c2w_stack && d->rnd && d->log, "lk_map_prepare: NULL batch buffer");
     LK_REQUIRE(!d->exposure || d->frame_id, "lk_map_prepare: exposure encoding needs frame_id");
     const MapWork wk = map_work(d->render.R, d->render.S, d->iters);
-    map_join_and_pregather(d, wk, d->render.R, d->exposure, (hipStream_t)stream_);
+    const int rc = map_join_and_pregather(d, wk, d->render.R, d->exposure, (hipStream_t)stream_);
+    if (rc != LK_OK) return rc;
     LK_LAUNCH_CHECK();
     return LK_OK;
 }
@@ -583,7 +585,10 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
     auto chunk_start = [&](int c) { return c == 0 ? 0 : 1 + (c - 1) * pre_chunk; };
     auto chunk_of = [&](int it) { return it == 0 ? 0 : 1 + (it - 1) / pre_chunk; };
     float* W0 = d->work;
-    if (pre && it_begin == 0 && (phases & 1) && !d->batches_ready) map_join_and_pregather(d, wk, R, xd, st);
+    if (pre && it_begin == 0 && (phases & 1) && !d->batches_ready) {
+        const int rc = map_join_and_pregather(d, wk, R, xd, st);
+        if (rc != LK_OK) return rc;
+    }
     // Ahead of the loop, on the third stream, a few iterations per chunk: the neighbour search (one launch per chunk) and,
     // per iteration, the counting sort of its rows by point for the feature-gradient gather (count, scan, place: lk_bwd2.hip) - both read
     // the rays, the positions and the row mask only.  Chunk c + 1 is enqueued when the loop reaches chunk c.
@@ -596,7 +601,8 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
         if (c0 >= d->iters) return LK_OK;
         PreStream& ps = pre_stream();
         hipStream_t pst = ps.ok ? ps.st : st;
-        if (ps.ok && c == 0) { (void)hipEventRecord(ps.e0, st); (void)hipStreamWaitEvent(pst, ps.e0, 0); }     // after k_pregather
+        if (ps.ok && c == 0) { LK_HIP_TRY(hipEventRecord(ps.e0, st)); LK_HIP_TRY(hipStreamWaitEvent(pst, ps.e0, 0)); }     // after k_pregather
+        if (ps.ok) { lk_debug_delay(LK_DELAY_LAUNCH, st); lk_debug_delay(LK_DELAY_AHEAD, pst); }
         const int c1 = chunk_start(c + 1) < d->iters ? chunk_start(c + 1) : d->iters, nc = c1 - c0;
         lk_render_desc sd = d->render;
         sd.flags = (d->render.flags & LK_FLAG_REL_POS) | LK_FLAG_ZERO_ABSENT;
@@ -613,6 +619,7 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
         sd.grad_row_mask = d->render.grad_row_mask;
         int rc = lk_presample(&sd, pst, counted ? &pc : nullptr);
         if (rc != LK_OK) return rc;
+        if (ps.ok && sort_ahead) lk_debug_delay(LK_DELAY_AHEAD, pst);
         for (int it = c0; sort_ahead && it < c0 + nc; it += LK_SEG_BATCH) {       // batches of consecutive iterations: five launches each
             const int nbatch = c0 + nc - it < LK_SEG_BATCH ? c0 + nc - it : LK_SEG_BATCH;
             const lk_knn_s* kn = d->render.knn;
@@ -631,7 +638,7 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
             rc = lk_launch_seg_sort(fs, counted, pst, nbatch);
             if (rc != LK_OK) return rc;
         }
-        if (ps.ok) (void)hipEventRecord(ps.ev[c % LK_PRE_CHUNKS], pst);
+        if (ps.ok) LK_HIP_TRY(hipEventRecord(ps.ev[c % LK_PRE_CHUNKS], pst));
         return LK_OK;
     };
     if (key_rows && it_begin == 0 && (phases & 1)) {
@@ -718,7 +725,7 @@ extern "C" int lk_map_frame(const lk_map_desc* d, int32_t it_begin, int32_t it_e
             }
             if ((phases & 1) && (it == chunk_start(ck) || it == it_begin)) {
                 PreStream& ps = pre_stream();
-                if (ps.ok) (void)hipStreamWaitEvent(st, ps.ev[ck % LK_PRE_CHUNKS], 0);
+                if (ps.ok) LK_HIP_TRY(hipStreamWaitEvent(st, ps.ev[ck % LK_PRE_CHUNKS], 0));
             }
         }
         if (phases & 1) {
