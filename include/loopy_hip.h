@@ -810,6 +810,59 @@ int lk_place_describe(const void* ws, int32_t H, int32_t W, int32_t n_levels, co
 int lk_place_match_score(const uint32_t* query, int32_t n_query, const uint32_t* db, const int32_t* counts, int32_t S, int32_t F,
                          int32_t max_hamming, int32_t* rows, int32_t* out_count, void* stream);
 
+/* ---------------------------------------------------------------- visual odometry
+ * The tracker's starting pose from the previous and the current RGB-D frame: the reference's tracking.visual_odometer
+ * (src/utils/visual_odometer.py, src/Tracker.py:92-97, 275-309), a multi-scale hybrid (intensity + depth) odometry after
+ * o3d.t.pipelines.odometry.  Open3D cannot be assumed: the contract is the arithmetic below, restated in NumPy by tests/odometry_referee.py,
+ * with two deliberate departures: bilinear instead of nearest-pixel lookups in the target frame, and a correct pose
+ * composition on the host.  NaN is the one "invalid" value throughout.  No floating-point atomic; equal inputs give equal bits.  fp32
+ * operations are rounded once each and taken in the order written.
+ *
+ * Pyramid of one frame (lk_odom_prepare), n_levels <= LK_ODOM_MAX_LEVELS levels, level l + 1 of size (h_l / 2) x (w_l / 2) (integer division)
+ * with all four intrinsics halved; the coarsest level must be 8 x 8 at least.  Level l holds LK_ODOM_PLANES planes of h_l w_l floats one after
+ * another from float offset off[l]: I, Vx, Vy, D, Ix, Iy, Dx, Dy.
+ *   Level 0: I = (0.299 r + 0.587 g) + 0.114 b; D = d where 0 < d <= max_depth, else NaN.
+ *   Level l + 1, pixel (y, x), centre (2y, 2x) of level l, K = [1 4 6 4 1] / 16:
+ *     I = sum_r K[r] (sum_k K[k] I_l[clamp(2y + r - 2)][clamp(2x + k - 2)]), both sums from index 0 up (rows filtered first, border replicated);
+ *     D = NaN where the centre c is NaN, else (sum K[r] K[k] v) / (sum K[r] K[k]) over the 5 x 5 neighbours v that are in bounds, not NaN and
+ *     have |v - c| <= depth_diff, r outer, k inner.
+ *   Per level: Vx = ((x - cx) / fx) D, Vy = ((y - cy) / fy) D (the vertex map is (Vx, Vy, D)); with the border replicated,
+ *     dx = (((p[y-1][x+1] + 2 p[y][x+1]) + p[y+1][x+1]) - ((p[y-1][x-1] + 2 p[y][x-1]) + p[y+1][x-1])) / 8 and dy likewise with rows and
+ *     columns exchanged, for p = I (Ix, Iy) and p = D (Dx, Dy); a depth derivative is NaN if any of its nine taps is.
+ *
+ * Estimate (lk_odom_estimate).  T (fp64 [16], row-major 4 x 4, device, in / out) maps source-camera points to target-camera points in the pinhole
+ * convention (x right, y down, z forward).  iters[n_levels] (host) are the iteration counts from the coarsest level to the finest (>= 0 each,
+ * LK_ODOM_MAX_ITERS in all); every iteration runs, there is no early exit and no host synchronisation.  One iteration at level l, with
+ * (R | t) = T rounded to fp32 and the level's intrinsics, for every source pixel whose D is not NaN, p = (Vx, Vy, D):
+ *   X = ((R00 px + R01 py) + R02 pz) + t0 and Y, Z alike; Z > 0;  uf = (fx X) / Z + cx, vf = (fy Y) / Z + cy;
+ *   u0 = floor(uf + 1/1024), a = clamp(uf - u0, 0, 1), v0 and b alike; 0 <= u0 < w_l - 1, 0 <= v0 < h_l - 1;
+ *   bil(M) = (1 - b) ((1 - a) M[v0][u0] + a M[v0][u0+1]) + b ((1 - a) M[v0+1][u0] + a M[v0+1][u0+1]) in the TARGET pyramid;
+ *   r_D = bil(D) - Z, (hx, hy) = bil(Dx), bil(Dy): all four taps of the three not NaN, and |r_D| <= outlier_trunc;
+ *   r_I = bil(I) - I_source, (gx, gy) = bil(Ix), bil(Iy);  iz = 1 / Z;
+ *   c0 = (gx fx) iz, c1 = (gy fy) iz, c2 = -((c0 X + c1 Y) iz), J_I = (-Z c1 + Y c2, Z c0 - X c2, -Y c0 + X c1, c0, c1, c2);
+ *   J_D = the same form from (hx, hy), plus (-Y, X, 0, 0, 0, -1);
+ *   w = 1 if |r| <= delta else delta / |r| (delta = huber_intensity, huber_depth); loss = r^2 / 2 or delta (|r| - delta / 2).
+ * Sums over the valid pixels, per lane in fp32, then lanes, half-waves and workgroups in a fixed order (workgroups in fp64):
+ *   A = sum w_I J_I J_I^T + w_D J_D J_D^T (upper triangle, rows first: 21), b = sum w_I r_I J_I + w_D r_D J_D (6), the loss, the count.
+ * Then A x = -b by Cholesky in fp64.  If the count is < 6 or a pivot is <= 0 (or NaN), T stays as it is and the record's flag is 1.  Otherwise
+ * T <- [exp(x0..2) | x3..5] T in fp64, exp by Rodrigues' formula.
+ * out_log (device, fp64 [sum iters][LK_ODOM_REC], or NULL), one record per iteration in the order run:
+ *   [0] level, [1] iteration, [2] valid count, [3] loss, [4..24] A, [25..30] b, [31] |x| (0 if flagged), [32] flag.
+ *
+ * lk_odom_ws_bytes: out_layout[4 + 2 LK_ODOM_MAX_LEVELS] = bytes of one pyramid, bytes of the estimate's scratch ws (8-byte aligned, contents on
+ * entry do not matter), LK_ODOM_PLANES, n_levels, then off[l] (in floats) and h_l w_l for l < LK_ODOM_MAX_LEVELS (0 beyond n_levels). */
+#define LK_ODOM_MAX_LEVELS 6
+#define LK_ODOM_MAX_PIXELS 16777216
+#define LK_ODOM_MAX_ITERS 100000
+#define LK_ODOM_PLANES 8
+#define LK_ODOM_REC 33
+int lk_odom_ws_bytes(int32_t H, int32_t W, int32_t n_levels, int64_t* out_layout /*[16]*/);
+int lk_odom_prepare(const float* color /*[H][W][3]*/, const float* depth /*[H][W]*/, int32_t H, int32_t W, int32_t n_levels, float fx, float fy,
+                    float cx, float cy, float max_depth, float depth_diff, float* pyr, void* stream);
+int lk_odom_estimate(const float* pyr_src, const float* pyr_tgt, int32_t H, int32_t W, int32_t n_levels, float fx, float fy, float cx, float cy,
+                     const int32_t* iters /*host, [n_levels], coarse to fine*/, float outlier_trunc, float huber_intensity, float huber_depth,
+                     double* T /*device, [16]*/, double* out_log, void* ws, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -40,6 +40,7 @@ ICP_POINT_TO_PLANE, ICP_INFORMATION, ICP_SUMS = 0, 1, 32
 FPFH_DIM, RANSAC_BEST = 33, 20
 ADAM_MAX_SEG = 16
 IMG_REC = 33
+ODOM_MAX_LEVELS, ODOM_PLANES, ODOM_REC = 6, 8, 33
 PLACE_BORDER, PLACE_BINS, PLACE_SEED, PLACE_NO_MATCH, PLACE_MAX_LEVELS = 20, 30, 0x4F524221, 257, 16
 
 _fp = C.c_void_p     # every device pointer crosses the ABI as an integer address
@@ -253,6 +254,11 @@ class LoopyLib:
             ('lk_place_detect', [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_place_describe', [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, C.c_void_p], C.c_int),
             ('lk_place_match_score', [_fp, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_odom_ws_bytes', [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)], C.c_int),
+            ('lk_odom_prepare', [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                 _fp, C.c_void_p], C.c_int),
+            ('lk_odom_estimate', [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32),
+                                  C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

@@ -22,7 +22,7 @@ import types
 import numpy as np
 import torch
 
-from . import _ffi, core, loop_closure, optim, parallel, steps, synthetic
+from . import _ffi, core, loop_closure, odometry, optim, parallel, steps, synthetic
 from .common import get_camera_from_tensor, get_tensor_from_camera, get_rays, get_samples, get_rays_from_uv
 
 
@@ -847,6 +847,16 @@ class Tracker:
         self.handle_dynamic = t.get('handle_dynamic', True)       # False: median-of-residual outlier mask (Tracker.py:177-179)
         self.gen = torch.Generator(device=self.eng.device).manual_seed(cfg.get('setup_seed', 1219) + 3)      # device draws (select_uv)
         self.last_log = None
+        # tracking.visual_odometer (Tracker.py:92-97): off (absent / False) makes no object and adds no launch
+        self.odometer = None
+        if t.get('visual_odometer', False):
+            self.odometer = odometry.VisualOdometer(self.eng, dict(H=self.H, W=self.W, fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy),
+                                                    t['visual_odometer'])
+
+    @property
+    def odometry_fallbacks(self):
+        """Frames whose odometry estimate was not usable and that started from the copied pose instead."""
+        return 0 if self.odometer is None else self.odometer.fallbacks
 
     def set_pipe(self, pipe):
         self.pipe = pipe
@@ -888,11 +898,17 @@ class Tracker:
         slam, eng = self.slam, self.eng
         if idx <= 1 or self.gt_camera:       # the first TWO frames keep the given pose (Tracker.py:297: `if idx <= 1 or self.gt_camera`)
             c2w = gt_c2w.clone()
+            if self.odometer is not None:    # Tracker.py:291-295
+                self.odometer.set_init_state(gt_color, gt_depth, gt_c2w)
         else:
             pre = slam.estimate_c2w_list[idx - 1].float()           # pose bookkeeping lives on the host (4x4 algebra)
             if self.const_speed_assumption and idx - 2 >= 0:
                 delta = pre @ torch.linalg.inv(slam.estimate_c2w_list[idx - 2].float())
                 init = delta @ pre
+            elif self.odometer is not None and idx - 2 >= 0:        # Tracker.py:304-309
+                # the previous frame's OPTIMISED pose is the base (Tracker.py:275-277, every frame here: one process, nothing to wait for)
+                self.odometer.update_est_abs_pose(slam.estimate_c2w_list[idx - 1])
+                init = self.odometer.estimate_pose(gt_color, gt_depth).float()
             else:
                 init = pre
             cam = get_tensor_from_camera(init)
