@@ -863,6 +863,35 @@ int lk_odom_estimate(const float* pyr_src, const float* pyr_tgt, int32_t H, int3
                      const int32_t* iters /*host, [n_levels], coarse to fine*/, float outlier_trunc, float huber_intensity, float huber_depth,
                      double* T /*device, [16]*/, double* out_log, void* ws, void* stream);
 
+/* ---------------------------------------------------------------- frame preparation
+ * A decoded frame -> what the trackers and mappers consume: colour float [Ho][Wo][3] in R, G, B and depth float [Ho][Wo] (the CPU passes of
+ * the reference's reader behind cv2.imread, src/utils/datasets.py:95-119; tests/datasets_referee.py states the same in NumPy
+ * float64).  The stages, in the reference's order, each skipped when it is the identity:
+ *   undistort   colour only, when `distortion` (HOST, [5] = k1 k2 p1 p2 k3) is given and not all zero.  Destination pixel (u, v), in double:
+ *               x = (u - cx) / fx, y = (v - cy) / fy, r2 = x x + y y, rad = ((1 + k1 r2) + k2 r2 r2) + k3 (r2 r2) r2,
+ *               x' = (x rad + ((2 p1) x) y) + p2 (r2 + (2 x) x), y' = (y rad + p1 (r2 + (2 y) y)) + ((2 p2) x) y, source = (fx x' + cx, fy y' + cy),
+ *               rounded to 1/32 pixel (rint of 32 s, half to even); the integer part picks the 2 x 2 taps, the two 5-bit fractions a, b the
+ *               integer weights 32 (32 - b)(32 - a), 32 (32 - b) a, 32 b (32 - a), 32 b a (they sum to 2^15); taps outside the image are 0;
+ *               result (sum w p + 2^14) >> 15 as uint8, into `undist` (device, [Hc][Wc][3], caller-owned: nothing is allocated here).
+ *   to float    colour float(c) / 255.0f, depth float(d) / png_depth_scale (fp32 divisions, correctly rounded).
+ *   resize      colour to the depth size when (Hc, Wc) != (Hd, Wd): source = (dst + 0.5) in / out - 0.5 clamped to [0, in - 1], bilinear.
+ *   crop_size   when crop_h, crop_w > 0: colour bilinear with source = dst (in - 1) / (out - 1); depth nearest, source =
+ *               min(floor(dst * fp32(in / out)), in - 1) (fp32 product).
+ *   crop_edge   rows and columns [e, size - e) of that: Ho = Hb - 2 e, Wo = Wb - 2 e with (Hb, Wb) = crop_size, else (Hd, Wd).
+ * Source cells and fractions of both float resamplings are formed in integers (quotient and remainder), the fraction by one fp32 division;
+ * a bilinear value is (1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11) in fp32; with both on, every crop tap composes its four
+ * resize taps on the fly (no intermediate float image).  At most two launches (the undistortion, then everything else), on `stream` only,
+ * no host synchronisation, no allocation.  LK_ERR_ARG: a NULL buffer (`undist` only when the undistortion runs), a size outside
+ * 1 .. LK_FRAME_MAX_DIM, flag bits other than the two below, crop_h / crop_w negative, only one of them 0, or one of them 1 (align_corners
+ * has no scale for it), crop_edge < 0 or 2 crop_edge >= Hb or Wb, png_depth_scale not finite and > 0, fx or fy == 0 with a distortion. */
+#define LK_FRAME_BGR 1u         /* colour bytes are B, G, R (cv2.imread); default R, G, B (Pillow) */
+#define LK_FRAME_DEPTH_F32 2u   /* depth is float [Hd][Wd]; default uint16 */
+#define LK_FRAME_MAX_DIM 16384
+int lk_frame_prepare(const uint8_t* color /*[Hc][Wc][3]*/, int32_t Hc, int32_t Wc, const void* depth /*[Hd][Wd]*/, int32_t Hd, int32_t Wd,
+                     uint32_t flags, float png_depth_scale, double fx, double fy, double cx, double cy, const double* distortion /*host [5] or NULL*/,
+                     int32_t crop_h, int32_t crop_w, int32_t crop_edge, uint8_t* undist /*[Hc][Wc][3] or NULL*/, float* out_color /*[Ho][Wo][3]*/,
+                     float* out_depth /*[Ho][Wo]*/, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Per-kernel GPU time with HIP events recorded on the launch stream around the selected kernels
  * (names: comma-separated, e.g. "k_decode_bwd", or "*").  lk_profile_end synchronises those events and writes

@@ -41,6 +41,7 @@ FPFH_DIM, RANSAC_BEST = 33, 20
 ADAM_MAX_SEG = 16
 IMG_REC = 33
 ODOM_MAX_LEVELS, ODOM_PLANES, ODOM_REC = 6, 8, 33
+FRAME_BGR, FRAME_DEPTH_F32, FRAME_MAX_DIM = 1, 2, 16384
 PLACE_BORDER, PLACE_BINS, PLACE_SEED, PLACE_NO_MATCH, PLACE_MAX_LEVELS = 20, 30, 0x4F524221, 257, 16
 
 _fp = C.c_void_p     # every device pointer crosses the ABI as an integer address
@@ -259,6 +260,8 @@ class LoopyLib:
                                  _fp, C.c_void_p], C.c_int),
             ('lk_odom_estimate', [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32),
                                   C.c_float, C.c_float, C.c_float, _fp, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_frame_prepare', [_fp, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_uint32, C.c_float, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_void_p], C.c_int),
         ):
             if hasattr(d, name):
                 fn = getattr(d, name)

@@ -12,7 +12,7 @@ per-frame bookkeeping in torch.  Loop closure's geometric back end (segment regi
 loop_closure.py, off by default (cfg['loop_closure']['enabled']); the final mesh (TSDF fusion of the mapped frames + marching
 cubes) is tsdf.py, off by default (cfg['meshing']['enabled']); the evaluation of the re-rendered frames and of the trajectory is
 render_eval.py, off by default (cfg['rendering_eval']['enabled']); place recognition is place.py
-(loop_closure.candidates: 'appearance'); datasets and visualisation stay out of scope (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
+(loop_closure.candidates: 'appearance'); the sequence readers are datasets.py; visualisation stays out of scope (SURVEY.md §2).  Every class takes an optional `eng` (core.Engine);
 the default is the gfx950 library on the current CUDA device.
 """
 import math
@@ -22,7 +22,7 @@ import types
 import numpy as np
 import torch
 
-from . import _ffi, core, loop_closure, odometry, optim, parallel, steps, synthetic
+from . import _ffi, core, datasets, loop_closure, odometry, optim, parallel, steps, synthetic
 from .common import get_camera_from_tensor, get_tensor_from_camera, get_rays, get_samples, get_rays_from_uv
 
 
@@ -1009,7 +1009,11 @@ class Point_SLAM:
             cfg['stop'] = getattr(args, 'stop', None)
         self.shared_decoders = NICER(cfg, eng=self.eng)
         self.load_pretrain(cfg)                 # Point_SLAM.py:94
-        self.frame_reader = dataset if dataset is not None else SyntheticRoomDataset(cfg, self.eng.device)
+        # the frames: a reader handed in; else the reader of cfg['dataset'] when data.input_folder holds a sequence of its layout
+        # (datasets.open_sequence; Point_SLAM.py:110); else the synthetic room
+        self.frame_reader = dataset if dataset is not None else datasets.open_sequence(cfg, args, eng=self.eng)
+        if self.frame_reader is None:
+            self.frame_reader = SyntheticRoomDataset(cfg, self.eng.device)
         self.n_img = len(self.frame_reader)
         self.estimate_c2w_list = torch.zeros((self.n_img, 4, 4))
         self.gt_c2w_list = torch.zeros((self.n_img, 4, 4))
@@ -1058,7 +1062,13 @@ class Point_SLAM:
         return self.pretrained_loaded
 
     def update_cam(self):
-        """crop_edge shifts the principal point and shrinks the image (Point_SLAM.py:155-175)."""
+        """crop_size rescales the intrinsics to the resized image, then crop_edge shifts the principal point and shrinks the image
+        (Point_SLAM.py:155-175)."""
+        crop_size = self.cfg['cam'].get('crop_size')
+        if crop_size:
+            sx, sy = crop_size[1] / self.W, crop_size[0] / self.H
+            self.fx, self.fy, self.cx, self.cy = sx * self.fx, sy * self.fy, sx * self.cx, sy * self.cy
+            self.W, self.H = crop_size[1], crop_size[0]
         e = self.cfg['cam'].get('crop_edge', 0) or 0
         if e > 0:
             self.H -= 2 * e

@@ -7,9 +7,10 @@ builds loopy_slam_amd.slam.Point_SLAM (same constructor arguments: cfg, args, ti
 after frame N with a checkpoint there (ckpt_freq = N, keyframe_every = 10, as the reference's deterministic-test mode does).
 `--wandb / --no_wandb` are accepted and ignored (logging is out of scope).
 
-Frames: the reference's dataset readers (src/utils/datasets.py: image decoding through cv2) are out of scope of this build and cv2 is
-not installed; when `data.input_folder` is not a directory of frames this build can read, the synthetic 640x480 room
-(loopy_slam_amd.synthetic) stands in at the config's intrinsics and the run says so.  A reader object with the reference's protocol
+Frames: when `data.input_folder` (or --input_folder) is a directory in the layout of the config's `dataset` - replica, scannet, azure,
+tumrgbd - the reader of loopy_slam_amd.datasets opens it (Pillow decodes, the device prepares the frames) and the run says so;
+tools/export_sequence.py writes such a directory from the synthetic room.  Otherwise the synthetic 640x480 room (loopy_slam_amd.synthetic)
+stands in at the config's intrinsics and the run says that.  A reader object with the reference's protocol
 (`len`, `[i] -> (idx, color [H,W,3], depth [H,W], c2w [4,4])` on the device) can be handed to Point_SLAM(dataset=...).
 """
 import argparse
@@ -20,7 +21,7 @@ import sys
 import numpy as np
 import torch
 
-from loopy_slam_amd import config
+from loopy_slam_amd import config, datasets
 from loopy_slam_amd.slam import Point_SLAM, Logger
 
 
@@ -64,13 +65,17 @@ def main(argv=None):
     from datetime import datetime
     time_string = datetime.now().strftime('%Y%m%d_%H%M%S') if args.stop is None else None
 
-    # Dataset readers (src/utils/datasets.py) are out of scope of this build: whatever data.input_folder says - an existing directory
-    # included - the frames come from the synthetic room, and every printed error is against ITS ground truth.  Said on every run.
-    folder = cfg['data'].get('input_folder')
-    print(f'run.py: NO FRAME READER in this build - data.input_folder = {folder!r} '
-          f'({"exists, NOT read" if (folder and os.path.isdir(folder)) else "not found"}): the synthetic room stands in '
-          f'({cfg["data"].get("n_frames", 50)} frames at the config\'s intrinsics); pass a dataset object to Point_SLAM(dataset=...) for real frames',
-          flush=True)
+    # Which frames: the config's reader when data.input_folder holds a sequence of its layout, else the synthetic room - and then every
+    # printed error is against ITS ground truth.  Said on every run.
+    folder, readable = datasets.sequence_folder(cfg, args)
+    if readable:
+        print(f'run.py: reading the {cfg["dataset"]} sequence in {folder!r} (loopy_slam_amd.datasets.{datasets.dataset_dict[cfg["dataset"]].__name__}, '
+              f'data.prefetch = {cfg["data"].get("prefetch", 2)})', flush=True)
+    else:
+        print(f'run.py: NO FRAME READER in this build - data.input_folder = {folder!r} '
+              f'({"exists, NOT read" if (folder and os.path.isdir(folder)) else "not found"}): the synthetic room stands in '
+              f'({cfg["data"].get("n_frames", 50)} frames at the config\'s intrinsics); pass a dataset object to Point_SLAM(dataset=...) for real frames',
+              flush=True)
     slam = Point_SLAM(cfg, args, time_string=time_string)
     slam.mapper.logger = Logger(cfg, args, slam.mapper)     # checkpoints in the reference's layout under <output>/ckpts (Point_SLAM.py:126-132)
     est, gt = slam.run()

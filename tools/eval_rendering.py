@@ -4,7 +4,7 @@
 the ATE of the last checkpoint's poses, into {output}/eval/rendering.json: the file a run with rendering_eval.enabled writes itself
 (loopy_slam_amd/render_eval.py; needs the GPU).
 
-    python tools/eval_rendering.py configs/Synthetic/room.yaml [--output DIR]
+    python tools/eval_rendering.py configs/Synthetic/room.yaml [--output DIR] [--input_folder DIR]
 """
 import argparse
 import os
@@ -15,13 +15,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
-from loopy_slam_amd import config, core, render_eval, slam
+from loopy_slam_amd import config, core, datasets, render_eval, slam
 from get_mesh_tsdf_fusion import last_checkpoint, rendered_frames
 
 
 def evaluate(eng, cfg, output, reader=None, write=True):
     """The result dict of the run in `output`; reader: the frames ([i] -> (idx, color, depth, c2w)), default the config's."""
-    reader = reader if reader is not None else slam.SyntheticRoomDataset(cfg, eng.device)
+    if reader is None:               # as Point_SLAM picks it: the config's reader on a sequence on disk, else the synthetic room
+        reader = datasets.open_sequence(cfg, None, eng=eng) or slam.SyntheticRoomDataset(cfg, eng.device)
     ck = last_checkpoint(output)
     n = int(ck['idx']) + 1
     est, gt = ck['estimate_c2w_list'][:n], ck['gt_c2w_list'][:n]
@@ -45,8 +46,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('config', type=str)
     ap.add_argument('--output', type=str)
+    ap.add_argument('--input_folder', type=str, help='the sequence the run read; overrides data.input_folder')
     args = ap.parse_args()
     cfg = config.load_config(args.config, os.path.join(ROOT, 'configs', 'point_slam.yaml'))
+    if args.input_folder:
+        cfg['data']['input_folder'] = args.input_folder
     output = args.output or cfg['data'].get('output', 'output')
     out = evaluate(core.Engine(), cfg, output)
     ms = 'none' if out['avg_ms_ssim'] is None else f"{out['avg_ms_ssim']:.4f}"

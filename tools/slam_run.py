@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end run of the drop-in API (Point_SLAM.run: track every frame, map every `every_frame`-th) on the synthetic
-room, the SURVEY 8(d) quality metrics beside the wall-clock rate:
+room - or, with --input_folder, on a sequence on disk through the config's reader (loopy_slam_amd.datasets) - the SURVEY 8(d) quality
+metrics beside the wall-clock rate:
 
   * frames/s through `Tracker.track_frame` / `Mapper.map_frame` (host code included; frames pre-rendered, the initial 1500-iteration
     mapping of frame 0 and the one-off start-up costs of the next `every_frame` frames reported separately),
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from loopy_slam_amd import slam, config  # noqa: E402
+from loopy_slam_amd import slam, config, datasets  # noqa: E402
 
 
 def align_rigid(est, gt):
@@ -61,9 +62,13 @@ class Preloaded:
         return self.frames[i]
 
 
-def run(cfg, frames, eng=None, sync=None):
+def run(cfg, frames, eng=None, sync=None, preload=True):
+    """preload=False: the frames are read while the clock runs (a sequence on disk: decode, upload and lk_frame_prepare are in the rate)."""
     ps = slam.Point_SLAM(cfg, None, eng=eng)
-    ps.frame_reader = Preloaded(ps.frame_reader)
+    on_disk = isinstance(ps.frame_reader, datasets.BaseDataset)
+    frames = len(ps.frame_reader)
+    if preload:
+        ps.frame_reader = Preloaded(ps.frame_reader)
     sync = sync or torch.cuda.synchronize
     stamps = []
 
@@ -111,7 +116,8 @@ def run(cfg, frames, eng=None, sync=None):
         'track_loss_first_last': [float(tl[0, 0]), float(tl[-1, 0])] if tl is not None else None,
         'map_loss_first_last': [float(ml[0, 0]), float(ml[-1, 0])] if ml is not None else None,
         'path_length_cm': round(100 * float((gt[1:, :3, 3] - gt[:-1, :3, 3]).norm(dim=1).sum()), 2),
-        'data': 'synthetic room, random-init decoders',
+        'data': (f"{cfg['dataset']} sequence in {cfg['data']['input_folder']}, prefetch {cfg['data'].get('prefetch', 2)}, "
+                 f"{'preloaded' if preload else 'read during the run'}" if on_disk else 'synthetic room') + ', random-init decoders',
         'ms_per_frame': [round(1e3 * float(x), 1) for x in per_frame],
     }
 
@@ -122,12 +128,24 @@ def main():
     ap.add_argument('--config', default='configs/Synthetic/room.yaml')
     ap.add_argument('--iters-first', type=int, default=None)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--input_folder', default=None, help='a sequence in the layout of the config\'s dataset (tools/export_sequence.py writes one); '
+                                                       'the synthetic room when it is not one')
+    ap.add_argument('--prefetch', type=int, default=None, help='data.prefetch: frames decoded ahead by the reader\'s thread (0 = off)')
+    ap.add_argument('--stream', action='store_true', help='read the frames during the run instead of before it')
+    ap.add_argument('--cam', default=None, help='H,W,fx,fy,cx,cy of the sequence when they are not the config\'s')
     args = ap.parse_args()
     cfg = config.load_config(args.config, 'configs/point_slam.yaml')
     cfg['data']['n_frames'] = args.frames
+    if args.input_folder is not None:
+        cfg['data']['input_folder'] = args.input_folder
+    if args.prefetch is not None:
+        cfg['data']['prefetch'] = args.prefetch
+    if args.cam:
+        v = [float(x) for x in args.cam.split(',')]
+        cfg['cam'].update(H=int(v[0]), W=int(v[1]), fx=v[2], fy=v[3], cx=v[4], cy=v[5])
     if args.iters_first is not None:
         cfg['mapping']['iters_first'] = args.iters_first
-    out = run(cfg, args.frames)
+    out = run(cfg, args.frames, preload=not args.stream)
     out['config'] = args.config
     print(json.dumps(out))
     if args.out:
