@@ -543,6 +543,19 @@ int lk_wgrad_single(const float* A, int32_t lda, int32_t a_mode, const float* A2
  * build are bit-identical, a rebuilt index may differ in the last bits. */
 int lk_normals(lk_knn_t knn, const float* pos, int64_t N, float radius, const float* host_camera3,
                float* out_normals /*[N,3]*/, uint8_t* out_valid /*[N]*/, void* stream);
+/* lk_normals_nn: the same over the max_nn NEAREST neighbours within the radius (Open3D's hybrid search; a segment's fused surface cloud holds
+ * on the order of a thousand vertices per 0.1-m ball, and the cap IS the support of a normal there).  For point i the candidates are all
+ * indexed points with contract distance d2 = (dx dx + dy dy) + dz dz <= fl(radius * radius), the point itself included - lk_normals' set.
+ * Of them the min(count, max_nn) smallest under the total order (d2, index) are selected: out_count[i] (or NULL) is that number,
+ * out_nbr[i][0 .. max_nn) (or NULL) their indices in that order, padded with -1.  The covariance runs over the selection, the sums relative
+ * to point i, in fp32, ADDED IN ASCENDING (d2, index) ORDER; then lk_normals' Jacobi, smallest eigenvector and flip towards host_camera3.
+ * Fewer than 3 selected points: out_valid[i] = 0 and a zero normal.  Selection and sum order are fixed by the cloud alone, so equal inputs
+ * give equal bits, also after the index is rebuilt (lk_normals cannot promise that).  No floating-point atomics.
+ * LK_ERR_ARG: max_nn < 1, max_nn > LK_NORMALS_MAX_NN, radius <= 0, N != the size of the index.  N = 0 is a no-op. */
+#define LK_NORMALS_MAX_NN 64
+int lk_normals_nn(lk_knn_t knn, const float* pos, int64_t N, float radius, int32_t max_nn, const float* host_camera3,
+                  float* out_normals /*[N,3]*/, uint8_t* out_valid /*[N]*/, int32_t* out_count /*[N] or NULL*/,
+                  int32_t* out_nbr /*[N][max_nn] or NULL*/, void* stream);
 /* One Gauss-Newton step's sums of point-to-plane ICP, or the sums of the correspondence information matrix.
  * Every source point p of src[P,3] is moved by the row-major 3 x 4 transform host_T12 (HOST pointer; three fused multiply-adds per
  * coordinate, s_x = fma(T00, p_x, fma(T01, p_y, fma(T02, p_z, T03))), so the identity reproduces p exactly); its correspondence is the
@@ -567,6 +580,10 @@ int lk_icp_accumulate(lk_knn_t tgt, const float* tgt_pos, const float* tgt_norma
  * multiply-adds per coordinate).  Rows whose matrix is exactly the identity, and rows with s outside [0, n_seg), keep their bits.
  * The neighbour index is stale afterwards: lk_knn_build. */
 int lk_apply_correction(float* pos, int64_t N, const int32_t* seg_id, const float* mats, int32_t n_seg, void* stream);
+/* In place on pos[N,3]: p <- R p + t with ONE row-major 3 x 4 matrix host_M12 (HOST pointer) for the whole array - a stored surface cloud
+ * of a segment, which has no label per row.  lk_apply_correction's arithmetic (three fused multiply-adds per coordinate); a matrix that is
+ * exactly the identity launches nothing, so the bits stay. */
+int lk_rigid_map(float* pos, int64_t N, const float* host_M12, void* stream);
 
 /* ---------------------------------------------------------------- loop closure: global start (FPFH + RANSAC)
  * What the reference's default "robust_icp" runs before its ICP (src/common.py: preprocess_point_cloud, execute_global_registration around

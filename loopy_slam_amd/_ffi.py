@@ -38,6 +38,7 @@ ERR_RANGE = -4
 EXPOSURE_MAX_F = 32
 ICP_POINT_TO_PLANE, ICP_INFORMATION, ICP_SUMS = 0, 1, 32
 FPFH_DIM, RANSAC_BEST = 33, 20
+NORMALS_MAX_NN = 64
 ADAM_MAX_SEG = 16
 IMG_REC = 33
 ODOM_MAX_LEVELS, ODOM_PLANES, ODOM_REC = 6, 8, 33
@@ -218,6 +219,8 @@ class LoopyLib:
             ('lk_map_wait_lists', [C.POINTER(MapDesc), C.c_int32, C.c_void_p], C.c_int),
             ('lk_map_wait_rows', [C.POINTER(MapDesc), C.c_void_p], C.c_int),
             ('lk_normals', [C.c_void_p, _fp, C.c_int64, C.c_float, C.POINTER(C.c_float), _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_normals_nn', [C.c_void_p, _fp, C.c_int64, C.c_float, C.c_int32, C.POINTER(C.c_float), _fp, _fp, _fp, _fp, C.c_void_p], C.c_int),
+            ('lk_rigid_map', [_fp, C.c_int64, C.POINTER(C.c_float), C.c_void_p], C.c_int),
             ('lk_icp_scratch_floats', [C.c_int64], C.c_int64),
             ('lk_icp_accumulate', [C.c_void_p, _fp, _fp, _fp, _fp, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, _fp,
                                    _fp, C.c_int64, _fp, C.c_void_p], C.c_int),

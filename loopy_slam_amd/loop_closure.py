@@ -2,7 +2,7 @@
 
 Reference                                                  here
   src/common.py  pairwise_registration (Open3D ICP)        register_pair -> icp -> lk_icp_accumulate (device sums, 6 x 6 solve on the host)
-  src/common.py  estimate_normals / orient_normals         estimate_normals -> lk_normals
+  src/common.py  estimate_normals / orient_normals         estimate_normals -> lk_normals, or lk_normals_nn (the max_nn nearest: Open3D's hybrid search)
   get_information_matrix_from_point_clouds                 information_matrix -> lk_icp_accumulate (LK_ICP_INFORMATION)
   src/common.py  register_point_cloud_pair                 register_pair's success rule
   o3d global_optimization (Levenberg-Marquardt)            optimize_pose_graph (host, fp64)
@@ -13,13 +13,17 @@ Reference                                                  here
 
   src/neural_point.py  ORB + DBoW query, compute_dbow_score  LoopCloser.appearance_candidates / on_mapped_frame -> place.PlaceRecognizer
 
+  src/neural_point.py  compute_tsdf (per-segment clouds)     LoopCloser.fuse_closed_segments -> tsdf.fuse_segment, extract_point_cloud; lk_rigid_map
+
 Which pairs are registered is `loop_closure.candidates`: 'pose' (the tracked keyframe poses), 'appearance' (place recognition: the
 library's own binary descriptor and matching score, place.py - not OpenCV's ORB, not a DBoW vocabulary) or a callable.  The
 methods 'icp' and 'robust_icp' start from the tracked poses (the identity between two segments of one world frame: the reference's
 method == "icp" branch, plus the Tukey fine stage of its "robust_icp" branch); 'fpfh_robust_icp' puts the reference's global start in
 front of them - voxel downsample, FPFH, mutual feature matches, 3-point RANSAC, all on the device - and survives a loop that has really
-drifted.  TSDF fusion and the error plots are out as well.  What is registered are the segments' NEURAL points (on the device, thinned by the insertion radius), not
-the raw back-projected sensor points the reference keeps per fragment.  Of the reference's edge filters only the
+drifted.  The error plots are out.  What is registered is `loop_closure.cloud`: 'neural' (default) = the segments' NEURAL points (on the
+device, thinned by the insertion radius), normals over every point within 0.1 m; 'tsdf' = what the reference registers - the sensor frames of
+every closed segment fused into a TSDF volume at the tracked poses, the mesh vertices kept per segment and moved with the map, normals over the
+50 nearest within 0.1 m; the pose graph then has one node per CLOSED segment.  Of the reference's edge filters only the
 `old_trans_mag_filter` branch (its default) is built.  Feature rows are not touched (rotation-agnostic in the reference too).
 """
 import ctypes as C
@@ -103,18 +107,21 @@ class SegmentCloud:
     0.3-m coarse search is the index's two-phase search (the box of one cell edge first, the full box only for a point with no
     neighbour that near), the 0.03-m fine search touches at most 2 x 2 rows."""
 
-    def __init__(self, eng, pos, camera, cell=NORMAL_RADIUS):
+    def __init__(self, eng, pos, camera, cell=NORMAL_RADIUS, max_nn=None, fpfh_max_nn=None):
+        """max_nn: the normals take the max_nn nearest neighbours within NORMAL_RADIUS (lk_normals_nn; the reference's 50 on a fused
+        surface cloud) instead of all of them (lk_normals); fpfh_max_nn: the same for the normals of the FPFH preprocessing (its 30)."""
         self.eng = eng
         self.pos = pos.detach().to(eng.device, torch.float32).contiguous()
         self.camera = np.asarray(torch.as_tensor(camera).detach().cpu().numpy(), dtype=np.float64).reshape(-1)[:3]
         self.cell = float(cell)
+        self.max_nn, self.fpfh_max_nn = max_nn, fpfh_max_nn
         self._knn = self._normals = None
         self._features = {}
 
     def features(self, voxel=VOXEL):
         """fpfh_features of this cloud, computed once per voxel size."""
         if voxel not in self._features:
-            self._features[voxel] = fpfh_features(self.eng, self.pos, self.camera, voxel)
+            self._features[voxel] = fpfh_features(self.eng, self.pos, self.camera, voxel, max_nn=self.fpfh_max_nn)
         return self._features[voxel]
 
     def __len__(self):
@@ -130,7 +137,7 @@ class SegmentCloud:
     @property
     def normals(self):
         if self._normals is None:
-            self._normals = estimate_normals(self.eng, self.pos, NORMAL_RADIUS, self.camera, knn=self.knn)
+            self._normals = estimate_normals(self.eng, self.pos, NORMAL_RADIUS, self.camera, knn=self.knn, max_nn=self.max_nn)
         return self._normals
 
     def close(self):
@@ -139,8 +146,9 @@ class SegmentCloud:
             self._knn = None
 
 
-def estimate_normals(eng, pos, radius=NORMAL_RADIUS, camera=(0.0, 0.0, 0.0), knn=None):
-    """(normals [N,3] f32, valid [N] uint8) of the cloud pos (lk_normals); knn: an index already built over pos."""
+def estimate_normals(eng, pos, radius=NORMAL_RADIUS, camera=(0.0, 0.0, 0.0), knn=None, max_nn=None):
+    """(normals [N,3] f32, valid [N] uint8) of the cloud pos; knn: an index already built over pos.  max_nn None: every point within the
+    radius (lk_normals); a number: the max_nn nearest of them under (d2, index) (lk_normals_nn, Open3D's hybrid search)."""
     pos = pos.contiguous()
     N = int(pos.shape[0])
     own = knn is None
@@ -149,11 +157,35 @@ def estimate_normals(eng, pos, radius=NORMAL_RADIUS, camera=(0.0, 0.0, 0.0), knn
         knn.build(pos)
     normals, valid = eng.zeros(N, 3), eng.zeros(N, dtype=torch.uint8)
     cam = (C.c_float * 3)(*[float(c) for c in np.asarray(camera, dtype=np.float64).reshape(-1)[:3]])
-    eng.lib.check(eng.lib.dll.lk_normals(knn.h, ptr(pos), N, C.c_float(radius), cam, ptr(normals), ptr(valid), eng.stream), 'lk_normals')
+    if max_nn is None:
+        eng.lib.check(eng.lib.dll.lk_normals(knn.h, ptr(pos), N, C.c_float(radius), cam, ptr(normals), ptr(valid), eng.stream), 'lk_normals')
+    else:
+        eng.lib.check(eng.lib.dll.lk_normals_nn(knn.h, ptr(pos), N, C.c_float(radius), int(max_nn), cam, ptr(normals), ptr(valid), None, None,
+                                                eng.stream), 'lk_normals_nn')
     if own:
         _sync(eng)
         knn.close()
     return normals, valid
+
+
+def normals_nn(eng, pos, knn, radius=NORMAL_RADIUS, max_nn=50, camera=(0.0, 0.0, 0.0), want_selection=True):
+    """lk_normals_nn with its selection: (normals [N,3] f32, valid [N] uint8, count [N] int32, nbr [N,max_nn] int32) - the last two None
+    without want_selection.  knn: the index built over pos."""
+    pos = pos.contiguous()
+    N = int(pos.shape[0])
+    normals, valid = eng.zeros(N, 3), eng.zeros(N, dtype=torch.uint8)
+    count = eng.empty(N, dtype=torch.int32) if want_selection else None
+    nbr = eng.empty(N, max(int(max_nn), 1), dtype=torch.int32) if want_selection else None
+    cam = (C.c_float * 3)(*[float(c) for c in np.asarray(camera, dtype=np.float64).reshape(-1)[:3]])
+    eng.lib.check(eng.lib.dll.lk_normals_nn(knn.h, ptr(pos), N, C.c_float(radius), int(max_nn), cam, ptr(normals), ptr(valid), ptr(count),
+                                            ptr(nbr), eng.stream), 'lk_normals_nn')
+    return normals, valid, count, nbr
+
+
+def rigid_map(eng, pos, T):
+    """pos [n,3] (contiguous, on the device) <- R pos + t in place, T 4 x 4 rounded to fp32 (lk_rigid_map; the identity keeps the bits)."""
+    M12 = (C.c_float * 12)(*np.asarray(T, dtype=np.float64)[:3, :4].astype(np.float32).ravel().tolist())
+    eng.lib.check(eng.lib.dll.lk_rigid_map(ptr(pos), int(pos.shape[0]), M12, eng.stream), 'lk_rigid_map')
 
 
 def icp_sums(eng, tgt, src_pos, T, max_dist, tukey_k=0.0, mode=_ffi.ICP_POINT_TO_PLANE, want_corr=False):
@@ -277,13 +309,13 @@ def fpfh(eng, pos, normals, valid, radius):
     return spfh, out
 
 
-def fpfh_features(eng, pos, camera, voxel=VOXEL):
-    """preprocess_point_cloud: downsample to `voxel`, normals over 2 voxels (towards `camera`), FPFH over 5 voxels.
-    Returns dict(pos, normals, valid, spfh, fpfh) on the device."""
+def fpfh_features(eng, pos, camera, voxel=VOXEL, max_nn=None):
+    """preprocess_point_cloud: downsample to `voxel`, normals over 2 voxels (towards `camera`; max_nn: over the nearest max_nn of them, the
+    reference's 30), FPFH over 5 voxels.  Returns dict(pos, normals, valid, spfh, fpfh) on the device."""
     down = voxel_downsample(eng, pos, voxel)
     knn = _canonical_index(eng, down, 2.0 * voxel)
     try:
-        normals, valid = estimate_normals(eng, down, 2.0 * voxel, camera, knn=knn)
+        normals, valid = estimate_normals(eng, down, 2.0 * voxel, camera, knn=knn, max_nn=max_nn)
         _sync(eng)
     finally:
         knn.close()
@@ -536,8 +568,16 @@ DEFAULTS = {'enabled': False, 'method': 'robust_icp', 'candidates': 'pose', 'max
             'global_conf': GLOBAL_CONF, 'global_iter': GLOBAL_ITER, 'global_seed': 0,      # these three: 'fpfh_robust_icp' only
             # candidates 'appearance' only.  min_score: midway between the two figures of profiles/place_recognition.md (the highest score
             # of two views 50 or more poses apart, the lowest of two within 5)
-            'min_score': MIN_SCORE, 'n_features': 500, 'n_levels': 8, 'max_hamming': 64}
+            'min_score': MIN_SCORE, 'n_features': 500, 'n_levels': 8, 'max_hamming': 64,
+            # what is registered.  'neural': the segments' neural points, normals over every point within NORMAL_RADIUS.  'tsdf': the
+            # reference's clouds - every sensor frame of a closed segment fused into a TSDF volume at the tracked poses, the mesh vertices
+            # kept (src/neural_point.py:960-1017); normals over the 50 nearest within the radius, the FPFH preprocessing's over 30
+            # (src/common.py:606-617, 545-549).  normals_max_nn: None = those defaults (no cap for 'neural'), a number overrides the 50.
+            # tsdf_every: frame stride inside a segment (1 = the reference)
+            'cloud': 'neural', 'normals_max_nn': None, 'tsdf_voxel_length': 5.0 / 512.0, 'tsdf_sdf_trunc': 0.04, 'tsdf_every': 1}
 CANDIDATES = ('pose', 'appearance')
+CLOUDS = ('neural', 'tsdf')
+SURFACE_MAX_NN, SURFACE_FPFH_MAX_NN = 50, 30               # src/common.py:606-617, 545-549
 
 
 def settings(cfg):
@@ -560,9 +600,17 @@ class LoopCloser:
             raise NotImplementedError(f"loop_closure.method {lc['method']!r}: one of {METHODS}")
         if not callable(lc['candidates']) and lc['candidates'] not in CANDIDATES:
             raise NotImplementedError(f"loop_closure.candidates {lc['candidates']!r}: one of {CANDIDATES} or a callable")
+        if lc['cloud'] not in CLOUDS:
+            raise NotImplementedError(f"loop_closure.cloud {lc['cloud']!r}: one of {CLOUDS}")
         tr = cfg.get('tracking', {})
         self.cfg, self.npc, self.slam, self.eng = lc, npc, slam, npc.eng
         self.method, self.candidates = lc['method'], lc['candidates']
+        # cloud 'tsdf': surface[i] = {'pos' [V,3], 'color' [V,3]} on the device, the fused sensor surface of every CLOSED segment i, moved with
+        # the map at every closure; the pose graph then has one node per closed segment (the reference's use_old_segments_only).  Empty otherwise.
+        self.tsdf = lc['cloud'] == 'tsdf'
+        self.surface = {}
+        self.max_nn = lc['normals_max_nn'] if lc['normals_max_nn'] is not None else (SURFACE_MAX_NN if self.tsdf else None)
+        self.fpfh_max_nn = SURFACE_FPFH_MAX_NN if self.tsdf else None
         # place recognition (the reference's values: configs/point_slam.yaml): owned in the 'appearance' mode only
         self.kval, self.dbow_filter, self.mult_dbow = int(tr.get('kval', 2)), bool(tr.get('dbow_filter', True)), float(tr.get('mult_dbow', 1.0))
         self.min_score = float(lc['min_score'])
@@ -588,7 +636,32 @@ class LoopCloser:
         return torch.nonzero(self.npc._seg[:self.npc.n] == i).reshape(-1)
 
     def segment_cloud(self, i, segments):
-        return SegmentCloud(self.eng, self.npc._pos[:self.npc.n][self.segment_rows(i)], segments[i]['est_c2w'][:3, 3])
+        """What is registered of segment i: its stored surface cloud (cloud 'tsdf') or its neural points."""
+        pos = self.surface[i]['pos'] if self.tsdf else self.npc._pos[:self.npc.n][self.segment_rows(i)]
+        return SegmentCloud(self.eng, pos, segments[i]['est_c2w'][:3, 3], max_nn=self.max_nn, fpfh_max_nn=self.fpfh_max_nn)
+
+    def fuse_closed_segments(self, segments):
+        """cloud 'tsdf': every closed segment without a surface cloud yet - in a run the one that has just closed, segment len(segments) - 2
+        - gets one: its frames [start, next start) stepped by tsdf_every, sensor depth and colour of slam.frame_reader at
+        slam.estimate_c2w_list (tsdf.fuse_segment), the vertices and colours of the volume kept, the volume dropped."""
+        from . import tsdf
+        slam, lc = self.slam, self.cfg
+        if slam is None:
+            raise ValueError("loop_closure.cloud 'tsdf' fuses the sensor frames of a segment: the closer needs the slam object (frame_reader, estimate_c2w_list)")
+        for i in range(len(segments) - 1):
+            if i in self.surface:
+                continue
+            idxs = [f for f in range(int(segments[i]['idx']), int(segments[i + 1]['idx']), max(int(lc['tsdf_every']), 1))
+                    if tsdf.pose_usable(slam.estimate_c2w_list[f])]
+
+            def frames():
+                for f in idxs:
+                    _, color, depth, _ = slam.frame_reader[f]
+                    yield depth, color
+            vol = tsdf.fuse_segment(self.eng, frames(), [slam.estimate_c2w_list[f] for f in idxs], slam.fx, slam.fy, slam.cx, slam.cy,
+                                    voxel_length=lc['tsdf_voxel_length'], sdf_trunc=lc['tsdf_sdf_trunc'])
+            cloud = vol.extract_point_cloud()
+            self.surface[i] = {'pos': cloud['vertices'].contiguous(), 'color': cloud['colors'].contiguous()}
 
     def pose_candidates(self, segments):
         """Pairs (newest, t): non-adjacent by more than tracking.min_dist, keyframe centres within max_center_dist metres and
@@ -655,7 +728,10 @@ class LoopCloser:
     # ---- one closure
     def compute_correction(self, segments):
         """Register the candidate pairs of the newest segment and optimise the pose graph.  Returns the optimize_pose_graph result,
-        or None when the newest segment got no loop edge (nothing is optimised then, as in the reference)."""
+        or None when the newest segment got no loop edge (nothing is optimised then, as in the reference).  cloud 'tsdf': the graph is
+        over the CLOSED segments, segments[:-1] - candidates, the "newest" node and the n < 3 rule included."""
+        if self.tsdf:
+            segments = segments[:-1]
         n = len(segments)
         self.last_edges, self.last_result, self.last_registrations = None, None, []
         if n < 3:
@@ -701,7 +777,13 @@ class LoopCloser:
         keyframes' poses, then rebuild the neighbour index."""
         nodes = np.asarray(pose_graph['nodes'] if isinstance(pose_graph, dict) else pose_graph, dtype=np.float64)
         n, npc, eng = len(segments), self.npc, self.eng
+        if self.tsdf and nodes.shape[0] == n - 1:
+            # one node per closed segment: the segment that has just opened (one frame so far) takes the matrix of the last closed one
+            # (src/neural_point.py:164-170)
+            nodes = np.concatenate([nodes, nodes[-1:]], 0)
         assert nodes.shape[0] == n
+        for i, sc in self.surface.items():
+            rigid_map(eng, sc['pos'], nodes[i])
         mats = torch.from_numpy(nodes[:, :3, :4].astype(np.float32).reshape(n, 12)).to(eng.device).contiguous()
         eng.lib.check(eng.lib.dll.lk_apply_correction(ptr(npc._pos), npc.n, ptr(npc._seg), ptr(mats), n, eng.stream), 'lk_apply_correction')
         if npc.n:
@@ -745,6 +827,8 @@ class LoopCloser:
         self.npc._seg[first_new_row:self.npc.n] = self.current_segment
         if self.place is not None:
             self.describe_segments(segments)
+        if self.tsdf:
+            self.fuse_closed_segments(segments)
         pg = self.compute_correction(segments)
         if pg is None:
             return None
@@ -760,4 +844,6 @@ class LoopCloser:
             out.append({'start_idx': int(sg['idx']), 'keyframe': sg['est_c2w'].detach().cpu(),
                         'n_points': int((self.npc._seg[:self.npc.n] == i).sum()),
                         'correction': torch.from_numpy(self.corrections[i] if i < len(self.corrections) else np.eye(4))})
+            if self.tsdf:
+                out[-1]['n_surface_points'] = int(self.surface[i]['pos'].shape[0]) if i in self.surface else 0
         return out

@@ -4,6 +4,7 @@ Reference                                                       here
   src/tools/get_mesh_tsdf_fusion.py  o3d ScalableTSDFVolume       TSDFVolume.integrate  -> lk_tsdf_touch + lk_tsdf_integrate
   volume.extract_triangle_mesh()                                  TSDFVolume.extract_triangle_mesh -> lk_mc_mark / _vertices / _triangles
   o3d.io.write_triangle_mesh                                      write_ply
+  src/neural_point.py  compute_tsdf (a segment's surface cloud)   fuse_segment + TSDFVolume.extract_point_cloud (loop_closure.cloud = 'tsdf')
 
 The class owns every buffer as a torch tensor.  Blocks of 16^3 voxels live in slots in allocation order (existing data never moves inside
 its slot); the sorted key array and the slot of each sorted key are rebuilt by a torch sort after each allocation.  Bookkeeping (unique,
@@ -285,6 +286,27 @@ def fuse_run(mapper, n_frames, ms=None, save_dir=None, on_frame=None):
                 np.save(os.path.join(save_dir, f'depth_{idx:05d}'), depth.cpu().numpy())
                 np.save(os.path.join(save_dir, f'color_{idx:05d}'), color.cpu().numpy())
         vol.integrate(depth, color, c2w, s.fx, s.fy, s.cx, s.cy)
+    return vol
+
+
+def pose_usable(c2w):
+    """A pose a frame can be fused at: finite, and written at all - Point_SLAM.estimate_c2w_list starts as zeros, and a mapper driven without
+    a tracker writes the mapped frames only (a rigid pose has a bottom row of 0 0 0 1)."""
+    c2w = torch.as_tensor(c2w)
+    return bool(torch.isfinite(c2w).all()) and float(c2w[3, 3]) == 1.0
+
+
+def fuse_segment(eng, frames, poses, fx, fy, cx, cy, voxel_length=5.0 / 512.0, sdf_trunc=0.04):
+    """The sensor frames of one map segment fused into a fresh volume at their poses (loop closure with `cloud: 'tsdf'`; the reference's
+    compute_tsdf, src/neural_point.py:960-1017).  frames: an iterable of (depth [H,W], color [H,W,3]); poses: the c2w [4,4] of each.  The
+    arithmetic of fuse_run(source='sensor'): the pose as fp32, one TSDFVolume.integrate per frame, in order.  A frame whose pose is not
+    usable (pose_usable) is skipped.  Returns the volume."""
+    vol = TSDFVolume(eng, voxel_length=voxel_length, sdf_trunc=sdf_trunc)
+    for (depth, color), c2w in zip(frames, poses):
+        c2w = torch.as_tensor(c2w).float()
+        if not pose_usable(c2w):
+            continue
+        vol.integrate(depth, color, c2w, fx, fy, cx, cy)
     return vol
 
 
